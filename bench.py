@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: tokens/sec of the Llama-3-8B training task (BASELINE.json metric).
 
-Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N>1 it is launched under
-``torch.distributed.run`` with one rank per GPU (RCCL over xGMI).  Started for N>1 WITHOUT a
+Contract (driver): ``python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]``;
+for N>1 it is launched under ``torch.distributed.run`` with one rank per GPU (RCCL over xGMI).  Started for N>1 WITHOUT a
 launcher (no ``WORLD_SIZE``), it starts ``torch.distributed.run`` itself as a child process; a
 ``WORLD_SIZE`` that differs from ``--gpus`` is an error (exit 2), never a silently smaller run.  W untimed warmup steps, then
 exactly K timed steps bracketed by barrier + ``torch.cuda.synchronize()``; the elapsed time is the
@@ -13,8 +13,16 @@ Weak scaling: each GPU processes ``--grad-accum`` × ``--micro-batch`` × ``--se
 step (default 8 × 1 × 8192).
 Data: synthetic random token ids; weights: random init (no network, no checkpoints).
 
-The orchestration half of the metric is measured literally, in a child process with its own time
-limit (``bench_apply.py``), at a moment when no rank of this benchmark holds a GPU:
+A plain run does only what the headline figure needs: set-up, the warmup, the K timed steps, the
+output files of ``--dump-outputs`` and the JSON line.
+
+``--dump-outputs DIR``: after the timed steps rank 0 writes what the LAST timed step computed, as
+``DIR/<name>.npy`` (see :func:`_dump_outputs`): its loss, the timed steps' losses and a fixed,
+seeded sample of the updated parameters and of the step's gradients.  Weights, data and the sample
+are functions of the arguments alone, so two builds can be compared output for output.
+
+``--full`` adds the orchestration half of the metric.  It is measured literally, in a child process
+with its own time limit (``bench_apply.py``), at a moment when no rank of this benchmark holds a GPU:
 
 * no launcher (N=1, or N>1 self-launched): in THIS process before any rank exists -- nothing here
   has touched the GPU yet, and the ranks are started only after the cold start has finished;
@@ -30,7 +38,8 @@ each land on a freshly created instance (``cold_start.stages_p50_s`` splits it: 
 launch, imports, rendezvous, extension load, GEMM selections, model init, first step);
 ``job_tokens_per_s`` is the tokens/s that task printed itself.  ``cold_start.control_plane`` keeps
 the control-plane-only number (submit -> first output of ``echo ready``, ``bench_coldstart.py``).
-Not included (local backend): VM boot, image pull, container start.  ``--no-coldstart`` skips it.
+Not included (local backend): VM boot, image pull, container start.  ``--no-coldstart`` skips it
+even with ``--full``.
 """
 
 from __future__ import annotations
@@ -163,6 +172,45 @@ def _release_gpu() -> None:
         dist.destroy_process_group()
 
 
+DUMP_SAMPLE = 4 * 1024 * 1024  # elements per sampled array: 16 MiB as float32
+
+
+def _dump_outputs(path: str, tr, res: dict) -> None:
+    """What a caller of the timed path holds after its last step, as float32/float64 ``.npy``:
+
+    * ``loss``            the loss the last timed step returned (float64, shape [1]);
+    * ``timed_losses``    the loss of every timed step, rounded to 4 decimals (float64, [steps]);
+    * ``params_sample``   the bf16 parameters after the last step's AdamW update (float32);
+    * ``grads_sample``    the gradients that step accumulated over its micro-batches (float32; one
+                          GPU only: with several ranks a rank holds only its reduced shard).
+
+    The two samples are the flat parameter / gradient buffers at ``DUMP_SAMPLE`` indices drawn once
+    from a fixed seed (the whole buffer when it is smaller), so they are the same elements in every
+    run with the same model."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    opt = tr.opt
+    opt.wait_params()  # the last step's all-gathers may still be in flight
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    np.save(os.path.join(path, "loss.npy"), np.asarray([res["final_loss"]], dtype=np.float64))
+    np.save(os.path.join(path, "timed_losses.npy"), np.asarray(res.get("losses") or [], dtype=np.float64))
+    total = opt.total_numel
+    if total > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(20240607).integers(0, total, DUMP_SAMPLE))
+        idx = torch.from_numpy(idx).to(opt.flat_param.device)
+        take = lambda t: t[idx]  # noqa: E731
+    else:
+        take = lambda t: t  # noqa: E731
+    arrays = {"params_sample": opt.flat_param}
+    if opt.world == 1:
+        arrays["grads_sample"] = opt.flat_grad
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), take(t.detach()).float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -178,16 +226,21 @@ def main():
     # (~36 ms/step on one GPU) and the ZeRO-1 collectives; same box, tokens/s: 2 -> 20.96k,
     # 4 -> 21.49k, 8 -> 21.81k (profiles/ab_r2l_grad_accum.txt)
     ap.add_argument("--grad-accum", type=int, default=8)
-    ap.add_argument("--no-coldstart", action="store_true", help="skip the dstack-apply cold-start half")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, parameter and gradient samples) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the dstack-apply cold-start half (a plain run times the training steps only)")
+    ap.add_argument("--no-coldstart", action="store_true", help="with --full: skip the dstack-apply cold-start half")
     ap.add_argument("--coldstart-timeout", type=float, default=600.0, help="time limit of one applied task run")
     ap.add_argument("--coldstart-fake-gpus", type=int, default=0, help=argparse.SUPPRESS)  # CPU tests
     args = ap.parse_args()
+    coldstart = args.full and not args.no_coldstart
 
     launched = "WORLD_SIZE" in os.environ
     cold = None
     if not launched:
         # no rank exists and nothing in this process has touched the GPU: the cold start runs now
-        if not args.no_coldstart:
+        if coldstart:
             cold = dict(_cold_start(args), when="before the benchmark's ranks started")
         if args.gpus > 1:
             sys.exit(_self_launch(args.gpus, sys.argv[1:], cold))
@@ -240,12 +293,14 @@ def main():
             "attn": os.environ.get("DSTACK_AMD_ATTN", "hip"),
             "device": torch.cuda.get_device_name(0) if torch.cuda.is_available() else "cpu",
         }
+    if args.dump_outputs and env.rank == 0:
+        _dump_outputs(args.dump_outputs, tr, res)
     tr.close()  # the optimizer's autograd hooks pin model and buffers from the C++ side
     del tr
     _release_gpu()
     if env.rank != 0:
         return
-    if launched and not args.no_coldstart:
+    if launched and coldstart:
         # external launcher: the other ranks have left; the applied task gets the whole node
         cold = dict(_cold_start(args), when="after the timed steps; benchmark ranks released their GPUs")
     print(json.dumps(_merge_cold(out, cold)), flush=True)

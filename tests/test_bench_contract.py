@@ -36,6 +36,35 @@ def test_bench_single_process_json():
     assert d["config"]["global_batch"] == 2 and d["config"]["seq_len"] == 64
 
 
+def test_bench_plain_run_skips_the_cold_start_and_dumps_repeatable_outputs(tmp_path):
+    """Without ``--full`` (and without ``--no-coldstart``) no task is applied: the JSON line has no
+    cold-start keys.  ``--dump-outputs`` writes the last timed step's loss, the timed losses and the
+    parameter / gradient samples as float32/float64 ``.npy``, equal from run to run."""
+    import numpy as np
+
+    plain = [a for a in ARGS if a != "--no-coldstart"]
+    dumps = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", *plain, "--dump-outputs", str(tmp_path / name)],
+                           cwd=REPO, env=_env(), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        (d,) = _json_lines(r.stdout)
+        assert KEYS <= set(d) and d["steps"] == 2 and d["ms_per_step"] > 0
+        assert not {"cold_start", "cold_start_p50_s", "job_tokens_per_s"} & set(d)
+        files = sorted(os.listdir(tmp_path / name))
+        assert files == ["grads_sample.npy", "loss.npy", "params_sample.npy", "timed_losses.npy"]
+        dumps.append({f: np.load(tmp_path / name / f) for f in files})
+    a, b = dumps
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    assert a["loss.npy"].shape == (1,) and a["timed_losses.npy"].shape == (2,)
+    assert abs(a["loss.npy"][0] - a["timed_losses.npy"][-1]) < 1e-4  # (the list is rounded to 4 decimals)
+    assert a["params_sample.npy"].shape == a["grads_sample.npy"].shape and a["params_sample.npy"].size > 0
+    assert np.abs(a["grads_sample.npy"]).max() > 0
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2**20
+    for f in a:
+        np.testing.assert_allclose(a[f], b[f], rtol=1e-5, atol=1e-7, err_msg=f)
+
+
 @pytest.mark.slow
 def test_bench_two_ranks_gloo():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
@@ -73,7 +102,9 @@ def test_bench_world_size_mismatch_is_an_error():
 
 
 def _cold_args():
-    return [a for a in ARGS if a != "--no-coldstart"] + ["--coldstart-fake-gpus", "2", "--coldstart-timeout", "240"]
+    # the cold-start half runs only with --full
+    return [a for a in ARGS if a != "--no-coldstart"] + ["--full", "--coldstart-fake-gpus", "2",
+                                                         "--coldstart-timeout", "240"]
 
 
 def _check_cold(d, n):

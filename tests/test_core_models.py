@@ -187,6 +187,33 @@ def test_reference_example_configurations(path):
     assert conf.type == data["type"]
 
 
+def _stored_reference_examples():
+    """The same configurations as stored settings (``tests/golden``), keyed by the example's path
+    in the reference repository: every field as the example has it, except that the shell lines
+    under ``commands`` / ``init`` are placeholders (any string is valid there).  Needs no
+    reference checkout, so it runs on every machine."""
+    import json
+
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
+                           "reference_example_configurations.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("rel,data", sorted(_stored_reference_examples().items()),
+                         ids=sorted(_stored_reference_examples()))
+def test_stored_reference_example_configurations(rel, data):
+    if rel in _KNOWN_INVALID:
+        with pytest.raises((ConfigurationError, ValidationError)):
+            parse_apply_configuration(data)
+        return
+    conf = parse_apply_configuration(data)
+    assert conf.type == data["type"]
+
+
+def test_stored_reference_examples_are_all_there():
+    assert len(_stored_reference_examples()) == 37 and _KNOWN_INVALID <= set(_stored_reference_examples())
+
+
 # ---- env / unix user / interpolation ----------------------------------------------------------
 def test_env_forms():
     assert Env(["A=1", "B=x=y"])["B"] == "x=y"

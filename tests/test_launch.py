@@ -28,9 +28,12 @@ def _run(args, tmp_path, timeout=60, **kw):
 
 
 def test_ranks_run_and_torch_is_not_imported_by_the_launcher(tmp_path):
+    # one write per rank: the ranks share the launcher's stdout, and ``print`` on an unbuffered
+    # stream (``python -u``) writes its arguments piece by piece, so their lines could interleave
     (tmp_path / "rank.py").write_text(
         "import os, sys\n"
-        "print('rank', os.environ['RANK'], os.environ['LOCAL_RANK'], os.environ['WORLD_SIZE'], sys.argv[1:])\n")
+        "sys.stdout.write('rank %s %s %s %s\\n' % (os.environ['RANK'], os.environ['LOCAL_RANK'], "
+        "os.environ['WORLD_SIZE'], sys.argv[1:]))\n")
     r = _run(["--nnodes=1", "--nproc-per-node", "3", "--master-port=29777", "rank.py", "--x", "1"], tmp_path)
     assert r.returncode == 0, r.stderr
     lines = sorted(ln for ln in r.stdout.splitlines() if ln.startswith("rank"))
