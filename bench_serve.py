@@ -4,6 +4,8 @@ latency of one model replica on one GPU, random-init weights, synthetic prompts.
 
     python bench_serve.py --model llama-3-70b --num-prompts 256 --input-len 1024 --output-len 256
     python bench_serve.py --model llama-3-70b --latency --input-len 32000 --output-len 128
+    python bench_serve.py --model llama-3-8b --num-prompts 64 --input-len 2048 --output-len 16 \
+        --shared-prefix-len 1536 --enable-prefix-caching
 
 Throughput mode submits every prompt at t=0 (like ``vllm benchmark_throughput``) and reports
 output and total tokens/s, TTFT / time-per-output-token percentiles, and the engine's prefill and
@@ -45,7 +47,14 @@ def main():
     ap.add_argument("--temperature", type=float, default=0.0)
     ap.add_argument("--quantization", choices=["fp8"], default=None)
     ap.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto")
+    ap.add_argument("--enable-prefix-caching", action="store_true",
+                    help="reuse cached KV pages of a shared prompt prefix (dstack_amd.serving --enable-prefix-caching)")
+    ap.add_argument("--shared-prefix-len", type=int, default=0,
+                    help="the first N tokens of every prompt are identical (a system prompt / template); the rest "
+                         "differ per prompt")
     args = ap.parse_args()
+    if not 0 <= args.shared_prefix_len <= args.input_len:
+        ap.error("--shared-prefix-len must be within --input-len")
 
     import numpy as np
     import torch
@@ -56,7 +65,8 @@ def main():
     t0 = time.perf_counter()
     eng = LLMEngine.from_model(args.model, max_model_len=max_len, max_batch=1 if args.latency else args.max_batch,
                                max_prefill_tokens=args.max_prefill_tokens, use_graphs=not args.no_graphs and None,
-                               quantization=args.quantization, kv_cache_dtype=args.kv_cache_dtype)
+                               quantization=args.quantization, kv_cache_dtype=args.kv_cache_dtype,
+                               enable_prefix_caching=args.enable_prefix_caching)
     t_load = time.perf_counter() - t0
     t0 = time.perf_counter()
     eng.capture_graphs()
@@ -66,13 +76,16 @@ def main():
     rng = np.random.default_rng(0)
     sp = SamplingParams(max_tokens=args.output_len, temperature=args.temperature, ignore_eos=True)
 
+    shared = rng.integers(10, vocab - 10, size=args.shared_prefix_len).tolist() if args.shared_prefix_len else []
+
     def prompts(n):
-        return [rng.integers(10, vocab - 10, size=args.input_len).tolist() for _ in range(n)]
+        return [shared + rng.integers(10, vocab - 10, size=args.input_len - len(shared)).tolist() for _ in range(n)]
 
     # warm-up: one short request through prefill and decode (hipBLASLt heuristics, allocator)
     eng.generate([prompts(1)[0][:128]], SamplingParams(max_tokens=4, ignore_eos=True))
     for k in eng.stats:
         eng.stats[k] = 0 if isinstance(eng.stats[k], int) else 0.0
+    hit0 = eng.sched.prefix_hit_tokens  # (the scheduler's totals include the warm-up request)
     torch.cuda.synchronize() if torch.cuda.is_available() else None
 
     n = args.repeats if args.latency else args.num_prompts
@@ -90,6 +103,7 @@ def main():
     e2e = [r.finished_at - r.arrival for r in reqs]
     tpot = [(r.finished_at - r.first_token_at) / max(1, len(r.output_ids) - 1) for r in reqs]
     st = eng.stats
+    hits = eng.sched.prefix_hit_tokens - hit0
     res = {
         "metric": "serving latency (s)" if args.latency else "serving output tokens/s",
         "value": round(_pct(e2e, 50), 4) if args.latency else round(out_tokens / elapsed, 1),
@@ -105,6 +119,10 @@ def main():
         "ttft_p50_s": round(_pct(ttft, 50), 4), "ttft_p99_s": round(_pct(ttft, 99), 4),
         "tpot_p50_ms": round(_pct(tpot, 50) * 1e3, 3), "e2e_p50_s": round(_pct(e2e, 50), 4),
         "prefill_tokens_per_s": round(st["prefill_tokens"] / st["prefill_s"], 1) if st["prefill_s"] else None,
+        # prompt tokens admitted (computed + served from the prefix cache) per second of prefill steps
+        "prompt_tokens_per_prefill_s": round((st["prefill_tokens"] + hits) / st["prefill_s"], 1) if st["prefill_s"] else None,
+        "prefix_caching": args.enable_prefix_caching, "shared_prefix_len": args.shared_prefix_len,
+        "prefix_hit_tokens": hits, "prefill_s": round(st["prefill_s"], 4),
         "decode_tokens_per_s": round(st["decode_tokens"] / st["decode_s"], 1) if st["decode_s"] else None,
         "engine_steps": st["steps"], "preemptions": st["preemptions"],
         "weights_gb": round(m.weight_bytes() / 1e9, 1), "kv_pages": m.num_pages, "kv_tokens": m.num_pages * 64,

@@ -35,6 +35,9 @@ hipError_t dsa_paged_decode(const void*, long, const void*, const void*, const i
                             float*, int, int, int, int, int, float, int, float, float, hipStream_t);
 hipError_t dsa_sample(const void*, long, int, int, const float*, const int64_t*, const int*, int*, float*,
                       hipStream_t);
+hipError_t dsa_paged_prefill(const void*, long, long, const void*, const void*, const int*, int, int, const int*,
+                             const int*, const int*, void*, int, int, int, int, float, int, float, float,
+                             hipStream_t);
 bool dsa_gemm_tn_supported(int, int, int);
 bool dsa_gemv_supported(int, int);
 hipError_t dsa_gemv(const void*, long, const void*, void*, long, int, int, int, hipStream_t);
@@ -897,6 +900,54 @@ void paged_decode(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
         "paged_decode");
 }
 
+// Causal attention of n segments of new tokens over the paged cache (csrc/paged_prefill.hip).
+// qkv: [rows, >= H*128] rows (the fused qkv output, read in place); out [rows, H*128] bf16: only rows
+// seg_offsets[s] + i, i < seg_lens[s], are written.  The query at that row sits at position
+// seg_starts[s] + i and attends to cache keys 0 .. seg_starts[s] + i of block_tables[s].
+// max_len: the longest segment when the caller knows it (it has then validated the plan itself);
+// < 0: the metadata is read back and validated here.
+void paged_prefill(torch::Tensor qkv, torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor block_tables,
+                   torch::Tensor seg_offsets, torch::Tensor seg_starts, torch::Tensor seg_lens, torch::Tensor out,
+                   int64_t H, int64_t KVH, double scale, double k_scale, double v_scale, int64_t max_len) {
+  TORCH_CHECK(qkv.is_cuda() && qkv.scalar_type() == torch::kBFloat16 && qkv.dim() == 2 && qkv.stride(1) == 1 &&
+                  qkv.size(1) >= H * 128 && qkv.stride(0) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(qkv.data_ptr()) % 16 == 0,
+              "qkv must be bf16 [rows, >= H*128] with contiguous, 16-byte aligned rows");
+  const bool fp8 = check_cache(k_cache, v_cache, KVH);
+  TORCH_CHECK(k_scale > 0 && v_scale > 0, "kv cache scales must be positive");
+  TORCH_CHECK(KVH > 0 && H % KVH == 0 && H / KVH <= 16, "paged_prefill: 1..16 query heads per KV head");
+  check_i32(block_tables, "block_tables");
+  check_i32(seg_offsets, "seg_offsets");
+  check_i32(seg_starts, "seg_starts");
+  check_i32(seg_lens, "seg_lens");
+  check_bf16(out, "out");
+  const int64_t n = seg_lens.numel(), rows = qkv.size(0), W = block_tables.dim() == 2 ? block_tables.size(1) : 0;
+  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) == n && W >= 1 && seg_offsets.numel() == n &&
+                  seg_starts.numel() == n && n <= 65535,
+              "paged_prefill: segment count mismatch");
+  TORCH_CHECK(out.numel() == rows * H * 128, "out must be [rows, H*128]");
+  if (n == 0) return;
+  if (max_len < 0) {
+    const auto of = seg_offsets.cpu(), st = seg_starts.cpu(), ln = seg_lens.cpu();
+    const int *o = of.data_ptr<int>(), *s = st.data_ptr<int>(), *l = ln.data_ptr<int>();
+    max_len = 0;
+    for (int64_t i = 0; i < n; ++i) {
+      TORCH_CHECK(s[i] >= 0 && l[i] >= 0 && o[i] >= 0 && (int64_t)o[i] + l[i] <= rows,
+                  "paged_prefill: segment ", i, " lies outside the ", rows, " rows of qkv");
+      TORCH_CHECK(l[i] == 0 || ((int64_t)s[i] + l[i] + 63) / 64 <= W, "paged_prefill: block table of width ", W,
+                  " does not cover segment ", i, " (", (int64_t)s[i] + l[i], " tokens)");
+      max_len = std::max<int64_t>(max_len, l[i]);
+    }
+  }
+  TORCH_CHECK(max_len <= rows, "paged_prefill: max_len exceeds the rows of qkv");
+  check(dsa_paged_prefill(qkv.data_ptr(), qkv.stride(0), rows, k_cache.data_ptr(), v_cache.data_ptr(),
+                          block_tables.data_ptr<int>(), (int)block_tables.stride(0), (int)W,
+                          seg_offsets.data_ptr<int>(), seg_starts.data_ptr<int>(), seg_lens.data_ptr<int>(),
+                          out.data_ptr(), (int)n, (int)max_len, (int)H, (int)KVH, (float)scale, fp8 ? 1 : 0,
+                          (float)k_scale, (float)v_scale, stream()),
+        "paged_prefill");
+}
+
 // tokens (int32 [rows]) and log-probs (fp32 [rows]) written in place; temps fp32, seeds int64, steps int32
 void sample(torch::Tensor logits, torch::Tensor temps, torch::Tensor seeds, torch::Tensor steps, torch::Tensor tokens,
             torch::Tensor logprobs) {
@@ -989,5 +1040,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("sin"), py::arg("k_cache"), py::arg("v_cache"), py::arg("H"), py::arg("KVH"), py::arg("k_scale"),
         py::arg("v_scale"), py::arg("rs") = py::none(), py::arg("cs") = py::none());
   m.def("paged_decode", &paged_decode);
+  m.def("paged_prefill", &paged_prefill, py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("block_tables"), py::arg("seg_offsets"), py::arg("seg_starts"), py::arg("seg_lens"), py::arg("out"),
+        py::arg("H"), py::arg("KVH"), py::arg("scale"), py::arg("k_scale"), py::arg("v_scale"),
+        py::arg("max_len") = -1);
   m.def("sample", &sample);
 }

@@ -22,44 +22,14 @@
 //    maximum context only, so the decode step can be captured once per batch bucket in a
 //    hipGraph.
 #include "common.h"
+#include "paged_frag.h"
 
 #include <type_traits>
 
 using namespace dsa;
+using namespace dsa::paged;
 
 namespace {
-
-constexpr int PAGE = 64;
-constexpr int HDIM = 128;
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4_t mfma16(const bf16x8_t& a, const bf16x8_t& b, const f32x4_t& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-__device__ __forceinline__ bf16x8_t ld8(const bf16_t* p) { return *reinterpret_cast<const bf16x8_t*>(p); }
-
-typedef unsigned int u2_t __attribute__((ext_vector_type(2)));
-
-// 8 e4m3 cache bytes (held raw while in flight: half the registers of bf16) -> the same bf16x8
-// MFMA operand the bf16 cache gives, converted right before the MFMA that reads it
-__device__ __forceinline__ bf16x8_t fp8x8_to_bf16(const u2_t w) {
-  bf16x8_t r;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8(w[h], false);
-    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8(w[h], true);
-    r[4 * h + 0] = (__bf16)lo[0];
-    r[4 * h + 1] = (__bf16)lo[1];
-    r[4 * h + 2] = (__bf16)hi[0];
-    r[4 * h + 3] = (__bf16)hi[1];
-  }
-  return r;
-}
 
 // one float -> one e4m3 byte (saturating at +-448)
 __device__ __forceinline__ unsigned char to_fp8(float x) {

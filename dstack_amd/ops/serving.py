@@ -1,7 +1,8 @@
-"""Serving ops: paged KV cache writes, paged decode attention and sampling.
+"""Serving ops: paged KV cache writes, paged decode attention, paged-prefix prefill attention and
+sampling.
 
-HIP kernels in ``csrc/paged_attn.hip`` for ROCm tensors; the PyTorch functions here are the CPU
-path of the engine and the fp32 references the GPU tests compare against.
+HIP kernels in ``csrc/paged_attn.hip`` and ``csrc/paged_prefill.hip`` for ROCm tensors; the PyTorch
+functions here are the CPU path of the engine and the fp32 references the GPU tests compare against.
 
 Cache layout (per layer): ``k_cache [pages, KVH, PAGE, 128]`` token-major and
 ``v_cache [pages, KVH, 128, PAGE]`` dim-major (see the kernel file for why), ``PAGE = 64``.
@@ -137,6 +138,63 @@ def paged_decode_ref(q, k_cache, v_cache, block_tables, ctx_lens, n_heads, n_kv_
         s = torch.einsum("hgd,hnd->hgn", qb, k) / math.sqrt(HEAD_DIM)
         p = torch.softmax(s, dim=-1)
         out[b] = torch.einsum("hgn,hnd->hgd", p, v).reshape(-1)
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
+# Paged-prefix prefill attention (prefix caching: new tokens over a cached prefix)
+# ----------------------------------------------------------------------------------------------
+def paged_prefill(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_tables: torch.Tensor,
+                  seg_offsets: torch.Tensor, seg_starts: torch.Tensor, seg_lens: torch.Tensor, n_heads: int,
+                  n_kv_heads: int, out: torch.Tensor | None = None, k_scale: float = 1.0, v_scale: float = 1.0,
+                  max_len: int | None = None) -> torch.Tensor:
+    """Causal attention of ``n`` segments of new tokens, packed in ``qkv`` [rows, >= H*128], over the
+    paged cache.  Segment s holds ``seg_lens[s]`` tokens from row ``seg_offsets[s]``; ``seg_starts[s]``
+    tokens of its sequence are cached already (any value >= 0).  The query at row
+    ``seg_offsets[s] + i`` sits at position ``seg_starts[s] + i`` and attends to cache keys
+    ``0 .. seg_starts[s] + i`` of ``block_tables[s]`` -- the segment's own K/V are read from the cache
+    too, where ``rope_cache_write`` has stored them.  Metadata: int32, ``block_tables`` [n, W].
+
+    Returns ``out`` [rows, H*128]; only the segments' rows are written.  ``max_len``: the longest
+    segment when the caller has it on the host (and has checked the plan); otherwise the HIP path
+    reads the metadata back to validate it and size its grid."""
+    rows = qkv.shape[0]
+    if out is None:
+        out = torch.zeros(rows, n_heads * HEAD_DIM, dtype=qkv.dtype, device=qkv.device)
+    if _ext.use_hip(qkv):
+        _ext.require().paged_prefill(qkv, k_cache, v_cache, block_tables, seg_offsets, seg_starts, seg_lens, out,
+                                     n_heads, n_kv_heads, 1.0 / math.sqrt(HEAD_DIM), k_scale, v_scale,
+                                     -1 if max_len is None else int(max_len))
+        return out
+    ref = paged_prefill_ref(qkv, k_cache, v_cache, block_tables, seg_offsets, seg_starts, seg_lens, n_heads,
+                            n_kv_heads, k_scale, v_scale)
+    for off, n in zip(seg_offsets.tolist(), seg_lens.tolist()):
+        out[off : off + n] = ref[off : off + n].to(out.dtype)
+    return out
+
+
+def paged_prefill_ref(qkv, k_cache, v_cache, block_tables, seg_offsets, seg_starts, seg_lens, n_heads, n_kv_heads,
+                      k_scale: float = 1.0, v_scale: float = 1.0):
+    """fp32 reference: gathers each segment's pages and runs masked softmax attention per row.
+    Returns [rows, H*128] fp32 with zeros outside the segments."""
+    G = n_heads // n_kv_heads
+    out = torch.zeros(qkv.shape[0], n_heads * HEAD_DIM, dtype=torch.float32, device=qkv.device)
+    ks, vs = (k_scale, v_scale) if _is_fp8(k_cache) else (1.0, 1.0)
+    for s in range(seg_lens.numel()):
+        off, start, n = int(seg_offsets[s]), int(seg_starts[s]), int(seg_lens[s])
+        if n <= 0:
+            continue
+        ctx = start + n
+        pages = block_tables[s, : (ctx + PAGE - 1) // PAGE].long()
+        k = k_cache[pages].float().permute(1, 0, 2, 3).reshape(n_kv_heads, -1, HEAD_DIM)[:, :ctx] * ks  # [KVH, ctx, D]
+        v = v_cache[pages].float().permute(1, 0, 3, 2).reshape(n_kv_heads, -1, HEAD_DIM)[:, :ctx] * vs
+        q = qkv[off : off + n, : n_heads * HEAD_DIM].float().view(n, n_kv_heads, G, HEAD_DIM)
+        sc = torch.einsum("ihgd,hkd->hgik", q, k) / math.sqrt(HEAD_DIM)
+        key = torch.arange(ctx, device=qkv.device)[None, :]
+        pos = start + torch.arange(n, device=qkv.device)[:, None]
+        sc = sc.masked_fill(key > pos, float("-inf"))
+        p = torch.softmax(sc, dim=-1)
+        out[off : off + n] = torch.einsum("hgik,hkd->ihgd", p, v).reshape(n, -1)
     return out
 
 

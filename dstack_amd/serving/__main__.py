@@ -27,6 +27,9 @@ def main(argv=None):
                     help="fp8: e4m3 projection weights with per-channel scales, per-token activation scales")
     ap.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto",
                     help="fp8: e4m3 paged KV cache (half the bytes per decode step, twice the tokens)")
+    ap.add_argument("--enable-prefix-caching", action="store_true",
+                    help="reuse the cached KV pages of a prompt's prefix (64-token pages, LRU eviction); "
+                         "not with tensor parallel")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
     log = logging.getLogger("dstack_amd.serving")
@@ -43,7 +46,7 @@ def main(argv=None):
     eng = LLMEngine.from_model(args.model, max_model_len=args.max_model_len, seed=args.seed, max_batch=args.max_batch,
                                max_prefill_tokens=args.max_prefill_tokens, use_graphs=not args.no_graphs and None,
                                gpu_memory_utilization=args.gpu_memory_utilization, quantization=args.quantization,
-                               kv_cache_dtype=args.kv_cache_dtype)
+                               kv_cache_dtype=args.kv_cache_dtype, enable_prefix_caching=args.enable_prefix_caching)
     eng.capture_graphs()
     m = eng.model
     log.info("model %s: %.1f GB weights, %d KV pages (%d tokens), max_model_len %d, %d graph buckets, ready in %.1fs",

@@ -12,6 +12,17 @@
 // running sequence).  Preemption = recompute: when a running sequence needs a new page and none
 // is free, the most recently admitted sequence releases its pages and goes back to the head of
 // the waiting queue with all its tokens as its new prompt (tokens stay with the caller).
+//
+// Automatic prefix caching (enable_prefix_caching, off by default): the scheduler also keeps every
+// sequence's token ids, and a FULL page whose K/V are all written becomes reusable.  A page is
+// identified by a chained hash of its parent page's hash and its own PAGE token ids; a hit is
+// confirmed by comparing the stored ids and the parent page (id and registration generation), so a
+// hash collision never hands out someone else's KV.  Pages carry reference counts; a registered
+// page whose count drops to zero keeps its hash entry on an LRU list of cached-free pages (a
+// sequence's pages are pushed tail first: leaves are evicted before their parents) and is evicted
+// only when the free list is empty.  Admission takes the hits of the prompt's full pages, always
+// leaving at least one token to compute; the plan's starts[i] = PAGE * hits, and the sequence's
+// first own slot is on a fresh page, so a shared page is never written.
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -19,6 +30,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <deque>
+#include <list>
 #include <stdexcept>
 #include <unordered_map>
 #include <vector>
@@ -35,14 +47,37 @@ struct Seq {
   int64_t admitted = -1;  // admission order (for preemption: newest first)
   bool running = false;
   std::vector<int32_t> pages;
+  // prefix caching
+  std::vector<int32_t> ids;  // token ids (prompt + appended), when the caller passes them
+  int start = 0;             // tokens taken from the cache at admission (a page multiple)
+  int chained = 0;           // leading pages that are hits or registered: the next page to register
+  uint64_t chain_hash = 0;   // hash of page chained - 1
+  bool chain_open = true;    // false once a page of this sequence could not be registered
 };
+
+// per-page state of the prefix cache
+struct PageInfo {
+  int ref = 0;
+  bool registered = false;
+  bool in_lru = false;
+  uint64_t hash = 0;
+  uint32_t gen = 0;          // bumped by every registration: a stale child never matches its parent
+  int32_t parent = -1;
+  uint32_t parent_gen = 0;
+  std::vector<int32_t> ids;  // the page's token ids while registered
+  std::list<int32_t>::iterator lru_it;
+};
+
+constexpr uint64_t HASH_SEED = 0x9e3779b97f4a7c15ULL;
 
 int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 class Scheduler {
  public:
-  Scheduler(int num_pages, int page_size, int max_batch, int max_prefill_tokens, int max_model_len, int pad_to)
-      : page_size_(page_size),
+  Scheduler(int num_pages, int page_size, int max_batch, int max_prefill_tokens, int max_model_len, int pad_to,
+            bool enable_prefix_caching)
+      : caching_(enable_prefix_caching),
+        page_size_(page_size),
         max_batch_(max_batch),
         max_prefill_tokens_(max_prefill_tokens),
         max_model_len_(max_model_len),
@@ -53,9 +88,10 @@ class Scheduler {
     for (int p = num_pages - 1; p >= 0; --p) free_.push_back(p);
     num_pages_ = num_pages;
     table_width_ = (max_model_len + page_size - 1) / page_size;
+    if (caching_) info_.resize(num_pages);
   }
 
-  void add(int64_t id, int prompt_len, int max_tokens) {
+  void add(int64_t id, int prompt_len, int max_tokens, const py::object& token_ids) {
     if (seqs_.count(id)) throw std::invalid_argument("scheduler: duplicate sequence id");
     if (prompt_len <= 0) throw std::invalid_argument("scheduler: empty prompt");
     if (prompt_len >= max_model_len_) throw std::invalid_argument("scheduler: prompt longer than max_model_len");
@@ -65,13 +101,21 @@ class Scheduler {
     s.id = id;
     s.num_tokens = prompt_len;
     s.max_tokens = std::min(max_tokens, max_model_len_);
+    if (!token_ids.is_none()) {
+      auto arr = py::array_t<int32_t, py::array::c_style | py::array::forcecast>::ensure(token_ids);
+      if (!arr || arr.ndim() != 1 || arr.shape(0) != prompt_len)
+        throw std::invalid_argument("scheduler: token_ids must be an int32 array of prompt_len entries");
+      if (caching_) s.ids.assign(arr.data(), arr.data() + prompt_len);
+    }
     seqs_[id] = std::move(s);
     waiting_.push_back(id);
   }
 
   // one more token was sampled for `id` (its K/V get written by the next decode step)
-  void append(int64_t id) {
+  // (`token`: its id, for the prefix cache; -1 = not given)
+  void append(int64_t id, int64_t token) {
     Seq& s = get(id);
+    if (caching_ && token >= 0 && (int)s.ids.size() == s.num_tokens) s.ids.push_back((int32_t)token);
     s.num_tokens += 1;
   }
 
@@ -79,6 +123,7 @@ class Scheduler {
   void mark_computed(int64_t id) {
     Seq& s = get(id);
     s.num_cached = s.num_tokens;
+    if (caching_) register_full_pages(s);
   }
 
   void finish(int64_t id) {
@@ -98,9 +143,10 @@ class Scheduler {
   // Plan the next step.  Returns a dict with
   //   kind: "prefill" | "decode" | "idle"
   //   seq_ids [n], preempted [k]
-  //   prefill: starts [n] (first token to compute = 0), lens [n] (tokens to compute), offsets [n]
-  //            (row of each sequence in the padded token buffer), rows (total padded rows),
-  //            positions [rows], slots [rows] (-1 on padding rows)
+  //   prefill: starts [n] (first token to compute: 0, or the cached prefix's length with prefix
+  //            caching), lens [n] (tokens to compute), offsets [n] (row of each sequence in the
+  //            padded token buffer), rows (total padded rows), positions [rows], slots [rows] (-1 on
+  //            padding rows); with prefix caching also block_tables [n, width] and ctx_lens [n]
   //   decode:  positions [n], slots [n], ctx_lens [n], block_tables [n, width]
   py::dict schedule(bool prefer_decode) {
     py::dict out;
@@ -112,12 +158,18 @@ class Scheduler {
       int rows = 0;
       while (!waiting_.empty() && (int)(running_.size() + ids.size()) < max_batch_) {
         Seq& s = get(waiting_.front());
-        const int need = pages_for(s.num_tokens + 1) - (int)s.pages.size();
-        const int padded = round_up(s.num_tokens, pad_to_);
+        // prefix caching: the registered pages that match the prompt's full pages (none otherwise)
+        int idle_hits = 0;  // hits that sit on the cached-free list: taking them uses up free pages
+        const std::vector<int32_t> hits = caching_ ? lookup(s, idle_hits) : std::vector<int32_t>{};
+        const int start = (int)hits.size() * page_size_;
+        const int need = pages_for(s.num_tokens + 1) - (int)s.pages.size() - (int)hits.size();
+        const int padded = round_up(s.num_tokens - start, pad_to_);
         if (!ids.empty() && rows + padded > max_prefill_tokens_) break;
-        if (need > (int)free_.size()) break;
+        if (need > free_pages() - idle_hits) break;
+        if (caching_) take_hits(s, hits);
         grow(s, s.num_tokens + 1);
-        s.num_cached = 0;
+        s.num_cached = start;
+        s.start = start;
         s.running = true;
         s.admitted = admit_counter_++;
         ids.push_back(s.id);
@@ -136,15 +188,30 @@ class Scheduler {
         int row = 0;
         for (int i = 0; i < n; ++i) {
           const Seq& s = get(ids[i]);
-          st(i) = 0;
-          ln(i) = s.num_tokens;
+          const int len = s.num_tokens - s.start;
+          st(i) = s.start;
+          ln(i) = len;
           of(i) = row;
-          const int padded = round_up(s.num_tokens, pad_to_);
+          const int padded = round_up(len, pad_to_);
           for (int t = 0; t < padded; ++t) {
-            ps(row + t) = t < s.num_tokens ? t : 0;
-            sl(row + t) = t < s.num_tokens ? slot_of(s, t) : -1;
+            ps(row + t) = t < len ? s.start + t : 0;
+            sl(row + t) = t < len ? slot_of(s, s.start + t) : -1;
           }
           row += padded;
+        }
+        if (caching_) {
+          py::array_t<int32_t> ctx(n);
+          py::array_t<int32_t> tables({n, table_width_});
+          auto cx = ctx.mutable_unchecked<1>();
+          auto tb = tables.mutable_unchecked<2>();
+          for (int i = 0; i < n; ++i) {
+            const Seq& s = get(ids[i]);
+            cx(i) = s.num_tokens;
+            const int np = (int)s.pages.size();
+            for (int j = 0; j < table_width_; ++j) tb(i, j) = j < np ? s.pages[j] : 0;
+          }
+          out["block_tables"] = tables;
+          out["ctx_lens"] = ctx;
         }
         out["kind"] = "prefill";
         out["seq_ids"] = ids;
@@ -171,7 +238,7 @@ class Scheduler {
     while (i < running_.size()) {
       Seq& s = get(running_[i]);
       bool self_preempted = false;
-      while (pages_for(s.num_tokens) > (int)s.pages.size() && free_.empty()) {
+      while (pages_for(s.num_tokens) > (int)s.pages.size() && free_pages() == 0) {
         const int64_t victim = running_.back();
         preempt(victim, preempted);
         if (victim == s.id) {
@@ -214,7 +281,14 @@ class Scheduler {
     return out;
   }
 
-  int free_pages() const { return (int)free_.size(); }
+  // free + cached-free (evictable) pages: what admission and preemption count on
+  int free_pages() const { return (int)(free_.size() + lru_.size()); }
+  int cached_pages() const { return (int)by_hash_.size(); }
+  int64_t prefix_hit_tokens() const { return hit_tokens_; }
+  int64_t prefix_query_tokens() const { return query_tokens_; }
+  bool prefix_caching() const { return caching_; }
+  // test hook: AND every page hash with `mask` (0: all pages collide), to exercise the id check
+  void test_set_hash_mask(uint64_t mask) { hash_mask_ = mask; }
   int num_pages() const { return num_pages_; }
   int num_waiting() const { return (int)waiting_.size(); }
   int num_running() const { return (int)running_.size(); }
@@ -240,14 +314,134 @@ class Scheduler {
   void grow(Seq& s, int tokens) {
     const int need = pages_for(tokens);
     while ((int)s.pages.size() < need) {
-      if (free_.empty()) throw std::runtime_error("scheduler: out of KV pages");
-      s.pages.push_back(free_.back());
+      if (free_.empty() && lru_.empty()) throw std::runtime_error("scheduler: out of KV pages");
+      if (free_.empty()) evict_lru();
+      const int32_t p = free_.back();
+      s.pages.push_back(p);
       free_.pop_back();
+      if (caching_) info_[p].ref = 1;
     }
   }
   void release(Seq& s) {
-    for (auto p : s.pages) free_.push_back(p);
+    if (!caching_) {
+      for (auto p : s.pages) free_.push_back(p);
+    } else {
+      // tail first: a leaf reaches the LRU list's head before its parents and is evicted first
+      for (auto it = s.pages.rbegin(); it != s.pages.rend(); ++it) {
+        PageInfo& pi = info_[*it];
+        if (--pi.ref > 0) continue;
+        if (pi.registered) {
+          pi.lru_it = lru_.insert(lru_.end(), *it);
+          pi.in_lru = true;
+        } else {
+          free_.push_back(*it);
+        }
+      }
+      s.start = s.chained = 0;
+      s.chain_hash = 0;
+      s.chain_open = true;
+    }
     s.pages.clear();
+  }
+
+  // ---- prefix cache ---------------------------------------------------------------------------
+  uint64_t page_hash(uint64_t parent_hash, const int32_t* ids) const {
+    uint64_t h = parent_hash ^ HASH_SEED;
+    for (int i = 0; i < page_size_; ++i) {  // splitmix64 finaliser over (h, id)
+      uint64_t z = h + 0x9e3779b97f4a7c15ULL + (uint64_t)(uint32_t)ids[i];
+      z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
+      z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
+      h = z ^ (z >> 31);
+    }
+    return h & hash_mask_;
+  }
+  // the registered page with this hash whose ids and parent are exactly these, or -1
+  int32_t find_page(uint64_t h, const int32_t* ids, int32_t parent) const {
+    auto range = by_hash_.equal_range(h);
+    for (auto it = range.first; it != range.second; ++it) {
+      const PageInfo& pi = info_[it->second];
+      if (pi.parent != parent || (parent >= 0 && pi.parent_gen != info_[parent].gen)) continue;
+      if (std::equal(pi.ids.begin(), pi.ids.end(), ids)) return it->second;
+    }
+    return -1;
+  }
+  // walk the prompt's full pages through the hash map; at least one token stays to be computed
+  std::vector<int32_t> lookup(const Seq& s, int& idle_hits) const {
+    std::vector<int32_t> hits;
+    idle_hits = 0;
+    if ((int)s.ids.size() < s.num_tokens) return hits;
+    const int cap = (s.num_tokens - 1) / page_size_;
+    uint64_t h = 0;
+    int32_t parent = -1;
+    for (int j = 0; j < cap; ++j) {
+      const int32_t* ids = s.ids.data() + (size_t)j * page_size_;
+      h = page_hash(h, ids);
+      const int32_t p = find_page(h, ids, parent);
+      if (p < 0) break;
+      hits.push_back(p);
+      if (info_[p].ref == 0) ++idle_hits;
+      parent = p;
+    }
+    return hits;
+  }
+  void take_hits(Seq& s, const std::vector<int32_t>& hits) {
+    for (auto p : hits) {
+      PageInfo& pi = info_[p];
+      if (pi.in_lru) {
+        lru_.erase(pi.lru_it);
+        pi.in_lru = false;
+      }
+      pi.ref += 1;
+      s.pages.push_back(p);
+    }
+    s.chained = (int)hits.size();
+    s.chain_hash = hits.empty() ? 0 : info_[hits.back()].hash;
+    s.chain_open = true;
+    query_tokens_ += s.num_tokens;
+    hit_tokens_ += (int64_t)hits.size() * page_size_;
+  }
+  // every page of `s` whose PAGE tokens' K/V are written becomes reusable (first registration of a
+  // content wins: an identical page computed by another sequence in the same step stays private,
+  // and with it the rest of that sequence's chain)
+  void register_full_pages(Seq& s) {
+    if (!s.running) return;
+    const int full = std::min(s.num_cached, (int)s.ids.size()) / page_size_;
+    while (s.chain_open && s.chained < full && s.chained < (int)s.pages.size()) {
+      const int j = s.chained;
+      const int32_t* ids = s.ids.data() + (size_t)j * page_size_;
+      const int32_t parent = j > 0 ? s.pages[j - 1] : -1;
+      const uint64_t h = page_hash(s.chain_hash, ids);
+      if (find_page(h, ids, parent) >= 0) {
+        s.chain_open = false;
+        break;
+      }
+      PageInfo& pi = info_[s.pages[j]];
+      pi.registered = true;
+      pi.hash = h;
+      pi.gen += 1;
+      pi.parent = parent;
+      pi.parent_gen = parent >= 0 ? info_[parent].gen : 0;
+      pi.ids.assign(ids, ids + page_size_);
+      by_hash_.emplace(h, s.pages[j]);
+      s.chain_hash = h;
+      s.chained = j + 1;
+    }
+  }
+  // the least recently released cached page loses its hash entry and becomes a free page
+  void evict_lru() {
+    const int32_t p = lru_.front();
+    lru_.pop_front();
+    PageInfo& pi = info_[p];
+    pi.in_lru = false;
+    auto range = by_hash_.equal_range(pi.hash);
+    for (auto it = range.first; it != range.second; ++it)
+      if (it->second == p) {
+        by_hash_.erase(it);
+        break;
+      }
+    pi.registered = false;
+    pi.ids.clear();
+    free_.push_back(p);
   }
   void preempt(int64_t id, std::vector<int64_t>& preempted) {
     Seq& s = get(id);
@@ -259,6 +453,12 @@ class Scheduler {
     preempted.push_back(id);
   }
 
+  bool caching_ = false;
+  std::vector<PageInfo> info_;                          // per page (prefix caching only)
+  std::unordered_multimap<uint64_t, int32_t> by_hash_;  // registered pages
+  std::list<int32_t> lru_;                              // cached-free pages, least recently released first
+  int64_t hit_tokens_ = 0, query_tokens_ = 0;
+  uint64_t hash_mask_ = ~0ULL;
   int page_size_, max_batch_, max_prefill_tokens_, max_model_len_, pad_to_;
   int num_pages_ = 0, table_width_ = 0;
   int64_t admit_counter_ = 0;
@@ -273,10 +473,13 @@ class Scheduler {
 PYBIND11_MODULE(_sched, m) {
   m.doc() = "dstack_amd serving: native continuous-batching scheduler and KV-page allocator";
   py::class_<Scheduler>(m, "Scheduler")
-      .def(py::init<int, int, int, int, int, int>(), py::arg("num_pages"), py::arg("page_size"),
-           py::arg("max_batch"), py::arg("max_prefill_tokens"), py::arg("max_model_len"), py::arg("pad_to") = 128)
-      .def("add", &Scheduler::add, py::arg("seq_id"), py::arg("prompt_len"), py::arg("max_tokens"))
-      .def("append", &Scheduler::append)
+      .def(py::init<int, int, int, int, int, int, bool>(), py::arg("num_pages"), py::arg("page_size"),
+           py::arg("max_batch"), py::arg("max_prefill_tokens"), py::arg("max_model_len"), py::arg("pad_to") = 128,
+           py::arg("enable_prefix_caching") = false)
+      .def("add", &Scheduler::add, py::arg("seq_id"), py::arg("prompt_len"), py::arg("max_tokens"),
+           py::arg("token_ids") = py::none())
+      .def("append", &Scheduler::append, py::arg("seq_id"), py::arg("token") = -1)
+      .def("_test_set_hash_mask", &Scheduler::test_set_hash_mask)
       .def("mark_computed", &Scheduler::mark_computed)
       .def("finish", &Scheduler::finish)
       .def("is_done", &Scheduler::is_done)
@@ -284,6 +487,10 @@ PYBIND11_MODULE(_sched, m) {
       .def("pages", &Scheduler::pages)
       .def("num_tokens", &Scheduler::num_tokens)
       .def_property_readonly("free_pages", &Scheduler::free_pages)
+      .def_property_readonly("cached_pages", &Scheduler::cached_pages)
+      .def_property_readonly("prefix_hit_tokens", &Scheduler::prefix_hit_tokens)
+      .def_property_readonly("prefix_query_tokens", &Scheduler::prefix_query_tokens)
+      .def_property_readonly("enable_prefix_caching", &Scheduler::prefix_caching)
       .def_property_readonly("num_pages", &Scheduler::num_pages)
       .def_property_readonly("num_waiting", &Scheduler::num_waiting)
       .def_property_readonly("num_running", &Scheduler::num_running)

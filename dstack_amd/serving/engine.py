@@ -61,6 +61,7 @@ class Request:
     finished_at: float | None = None
     on_event: object = None
     seed: int = 0
+    cached_tokens: int = 0  # prompt tokens taken from the prefix cache at admission
 
     @property
     def all_ids(self):
@@ -79,9 +80,12 @@ def _buckets(max_batch: int):
 class LLMEngine:
     def __init__(self, model: ServingLlama, max_batch: int = 256, max_prefill_tokens: int = 16384,
                  num_pages: int | None = None, use_graphs: bool | None = None, gpu_memory_utilization: float = 0.90,
-                 eos_token_ids=()):
+                 eos_token_ids=(), enable_prefix_caching: bool = False):
         from dstack_amd.serving import _native
 
+        if enable_prefix_caching and model.tp > 1:
+            raise ValueError("prefix caching is not supported with tensor parallel yet")
+        self.prefix_caching = bool(enable_prefix_caching)
         self.model = model
         self.device = model.device
         self.tp, self.tp_group = model.tp, model.tp_group
@@ -98,7 +102,8 @@ class LLMEngine:
         self.max_batch = max_batch
         self.sched = _native.Scheduler(num_pages=model.num_pages, page_size=sops.PAGE, max_batch=max_batch,
                                        max_prefill_tokens=max(max_prefill_tokens, model.max_model_len),
-                                       max_model_len=model.max_model_len, pad_to=128)
+                                       max_model_len=model.max_model_len, pad_to=128,
+                                       enable_prefix_caching=self.prefix_caching)
         self.width = self.sched.table_width
         self.eos_token_ids = tuple(eos_token_ids)
         self.requests: dict[int, Request] = {}
@@ -114,10 +119,15 @@ class LLMEngine:
         self._graphs: dict[int, torch.cuda.CUDAGraph] = {}
         self._alloc_static()
         self.stats = dict(prefill_tokens=0, decode_tokens=0, steps=0, preemptions=0, prefill_s=0.0, decode_s=0.0)
+        if self.prefix_caching:
+            # (prefill_tokens counts computed tokens: an admitted prompt is its hit + computed tokens)
+            self.stats.update(prefix_hit_tokens=0, prefix_query_tokens=0, prefix_cached_pages=0)
 
     @classmethod
     def from_model(cls, model: str, device=None, max_model_len: int | None = None, seed: int = 0, tp_group=None,
                    quantization: str | None = None, kv_cache_dtype: str = "auto", **kw):
+        if kw.get("enable_prefix_caching") and tp_group is not None:
+            raise ValueError("prefix caching is not supported with tensor parallel yet")
         spec = load_spec(model)
         device = device or ("cuda" if torch.cuda.is_available() else "cpu")
         m = ServingLlama(spec, device, max_model_len=max_model_len, tp_group=tp_group, quantization=quantization,
@@ -219,7 +229,11 @@ class LLMEngine:
         for req in pending:
             if req.finished:
                 continue
-            self.sched.add(req.id, len(req.prompt_ids), len(req.prompt_ids) + req.params.max_tokens)
+            if self.prefix_caching:
+                self.sched.add(req.id, len(req.prompt_ids), len(req.prompt_ids) + req.params.max_tokens,
+                               np.asarray(req.prompt_ids, dtype=np.int32))
+            else:
+                self.sched.add(req.id, len(req.prompt_ids), len(req.prompt_ids) + req.params.max_tokens)
         for rid in aborted:
             self.sched.finish(rid)
             self._emit(self.requests.pop(rid, None), None, True)
@@ -242,21 +256,30 @@ class LLMEngine:
         t0 = time.perf_counter()
         if kind == "prefill":
             toks = np.zeros(plan["rows"], dtype=np.int64)
-            for r, off, n in zip(reqs, plan["offsets"], plan["lens"]):
-                toks[off : off + n] = r.all_ids[:n]
+            for r, off, n, st in zip(reqs, plan["offsets"], plan["lens"], plan["starts"]):
+                toks[off : off + n] = r.all_ids[st : st + n]
+                if not r.output_ids:  # (a readmission after preemption also hits generated tokens)
+                    r.cached_tokens = int(st)
             if self.tp > 1:
                 self._bcast_prefill(toks, plan["positions"], plan["slots"], plan["offsets"], plan["lens"])
             dev = self.device
             logits = self.model.prefill(torch.from_numpy(toks).to(dev), torch.from_numpy(plan["positions"]).to(dev),
-                                        torch.from_numpy(plan["slots"]).to(dev), plan["offsets"], plan["lens"])
+                                        torch.from_numpy(plan["slots"]).to(dev), plan["offsets"], plan["lens"],
+                                        **(dict(starts=plan["starts"], block_tables=plan["block_tables"])
+                                           if self.prefix_caching else {}))
             tokens, lps = self._sample(logits, reqs)
             self.stats["prefill_tokens"] += int(sum(plan["lens"]))
+            if self.prefix_caching:
+                self.stats.update(prefix_hit_tokens=self.sched.prefix_hit_tokens,
+                                  prefix_query_tokens=self.sched.prefix_query_tokens)
             self.stats["prefill_s"] += time.perf_counter() - t0
         else:
             tokens, lps = self._decode(plan, reqs)
             self.stats["decode_tokens"] += len(reqs)
             self.stats["decode_s"] += time.perf_counter() - t0
         self.stats["steps"] += 1
+        if self.prefix_caching:
+            self.stats["prefix_cached_pages"] = self.sched.cached_pages
         now = time.perf_counter()
         for req, tok, lp in zip(reqs, tokens, lps):
             self.sched.mark_computed(req.id)
@@ -267,7 +290,10 @@ class LLMEngine:
             req.logprobs.append(float(lp))
             if req.first_token_at is None:
                 req.first_token_at = now
-            self.sched.append(req.id)
+            if self.prefix_caching:
+                self.sched.append(req.id, tok)
+            else:
+                self.sched.append(req.id)
             reason = None
             if len(req.output_ids) >= req.params.max_tokens:
                 reason = "length"
@@ -434,6 +460,8 @@ class LLMEngine:
                     self._emit(r, None, True)
 
     def metrics(self) -> dict:
+        if self.prefix_caching:
+            self.stats["prefix_cached_pages"] = self.sched.cached_pages
         return dict(self.stats, running=self.sched.num_running, waiting=self.sched.num_waiting + len(self._pending),
                     kv_pages_free=self.sched.free_pages, kv_pages_total=self.sched.num_pages,
                     kv_usage=1.0 - self.sched.free_pages / max(1, self.sched.num_pages))

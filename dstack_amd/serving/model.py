@@ -694,11 +694,20 @@ class ServingLlama:
     # forward passes
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def prefill(self, tokens: torch.Tensor, positions: torch.Tensor, slots: torch.Tensor, offsets, lens):
+    def prefill(self, tokens: torch.Tensor, positions: torch.Tensor, slots: torch.Tensor, offsets, lens,
+                starts=None, block_tables=None):
         """Prompts packed into 128-row-aligned segments of one token buffer (``offsets[i]`` is the
         first row of prompt i, ``lens[i]`` its length; padding rows have slot -1).  Writes every
         prompt token's K/V into the cache and returns the logits of each prompt's last token
-        [n, vocab]."""
+        [n, vocab].
+
+        Prefix caching: ``starts[i]`` > 0 says that the first ``starts[i]`` tokens of prompt i are in
+        the cache already (pages ``block_tables[i]``, [n, W] int32) and segment i holds only the
+        ``lens[i]`` tokens after them.  Such segments attend through the paged cache
+        (``sops.paged_prefill``, one launch per layer, after the layer's cache write); segments with
+        ``starts[i] == 0`` keep the flash-attention path over their own rows.  With an fp8 KV cache a
+        hit segment therefore reads its own chunk's K/V back in e4m3 (as every decode step does),
+        where the flash path uses the bf16 projections."""
         H, KVH = self.H, self.KVH
         rows = tokens.numel()
         x = F.embedding(tokens, self.embed)
@@ -710,7 +719,23 @@ class ServingLlama:
         # consecutive segments of one length attend as one batch (one kernel launch instead of one
         # per prompt: a 1024-token prompt alone fills 256 workgroups of a 70B layer)
         groups: list[list[int]] = []
-        for off, n in bounds:
+        hit = [i for i in range(len(lens)) if starts is not None and int(starts[i]) > 0]
+        if hit:
+            if block_tables is None:
+                raise ValueError("prefill: segments with a cached prefix need their block tables")
+            W = block_tables.shape[1]
+            for i in hit:
+                if int(lens[i]) > bounds[i][1] or (int(starts[i]) + int(lens[i]) + sops.PAGE - 1) // sops.PAGE > W:
+                    raise ValueError(f"prefill: segment {i} does not fit its rows or its block table")
+            i32 = dict(dtype=torch.int32, device=x.device)
+            hit_tables = torch.as_tensor(block_tables).to(**i32)[torch.tensor(hit, device=x.device)].contiguous()
+            hit_off = torch.tensor([bounds[i][0] for i in hit], **i32)
+            hit_start = torch.tensor([int(starts[i]) for i in hit], **i32)
+            hit_len = torch.tensor([int(lens[i]) for i in hit], **i32)
+            hit_max = max(int(lens[i]) for i in hit)
+        for i, (off, n) in enumerate(bounds):
+            if i in hit:
+                continue
             g = groups[-1] if groups else None
             if g is not None and g[1] == n and g[0] + g[1] * g[2] == off:
                 g[2] += 1
@@ -737,7 +762,11 @@ class ServingLlama:
                     qkv = qkv + L["bqkv"]
                 sops.rope_cache_write(qkv, positions, slots, self.cos, self.sin, self.k_cache[li], self.v_cache[li],
                                       H, KVH, self.k_scale, self.v_scale)
-            o = torch.empty(rows, H * self.D, dtype=x.dtype, device=x.device)
+            # (a hit segment's padding rows are not written by the paged kernel: keep them finite)
+            o = (torch.zeros if hit else torch.empty)(rows, H * self.D, dtype=x.dtype, device=x.device)
+            if hit:
+                sops.paged_prefill(qkv, self.k_cache[li], self.v_cache[li], hit_tables, hit_off, hit_start, hit_len,
+                                   H, KVH, out=o, k_scale=self.k_scale, v_scale=self.v_scale, max_len=hit_max)
             for off, n, cnt in groups:
                 seg = qkv[off : off + n * cnt].view(cnt, n, -1)
                 if self.hip:

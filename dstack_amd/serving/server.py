@@ -58,6 +58,13 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
     tok = tokenizer or load_tokenizer(engine.model.spec.path, engine.model.cfg.vocab_size)
     if not engine.eos_token_ids:
         engine.eos_token_ids = tuple(tok.eos_token_ids)
+    def _usage(prompt_tokens: int, completion_tokens: int, reqs) -> dict:
+        u = {"prompt_tokens": prompt_tokens, "completion_tokens": completion_tokens,
+             "total_tokens": prompt_tokens + completion_tokens}
+        if engine.prefix_caching:  # prompt tokens served from the prefix cache (OpenAI's field for it)
+            u["prompt_tokens_details"] = {"cached_tokens": sum(r.cached_tokens for r in reqs)}
+        return u
+
     state = dict(requests=0, ttft_sum=0.0, ttft_n=0, gen_tokens=0, prompt_tokens=0, started=time.time())
 
     from contextlib import asynccontextmanager
@@ -214,7 +221,7 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
                 finally:
                     _abort_all(subs)  # the client left mid-stream: later choices were never read
                 if (body.get("stream_options") or {}).get("include_usage"):
-                    usage["total_tokens"] = usage["prompt_tokens"] + usage["completion_tokens"]
+                    usage = _usage(usage["prompt_tokens"], usage["completion_tokens"], [s[1][0] for s in subs])
                     yield "data: " + json.dumps({"id": rid, "object": "text_completion", "created": created,
                                                  "model": served_model_name, "choices": [], "usage": usage}) + "\n\n"
                 yield "data: [DONE]\n\n"
@@ -237,7 +244,7 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
         finally:
             _abort_all(subs)
         return {"id": rid, "object": "text_completion", "created": created, "model": served_model_name,
-                "choices": choices, "usage": {"prompt_tokens": pt, "completion_tokens": ct, "total_tokens": pt + ct}}
+                "choices": choices, "usage": _usage(pt, ct, [s[1][0] for s in subs])}
 
     @app.post("/v1/chat/completions")
     async def chat(request: Request):
@@ -262,8 +269,7 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
                     yield "data: " + json.dumps(dict(head, choices=[{"index": 0, "delta": d,
                                                                     "finish_reason": reason}])) + "\n\n"
                 if (body.get("stream_options") or {}).get("include_usage"):
-                    u = {"prompt_tokens": len(ids), "completion_tokens": len(req.output_ids),
-                         "total_tokens": len(ids) + len(req.output_ids)}
+                    u = _usage(len(ids), len(req.output_ids), [req])
                     yield "data: " + json.dumps(dict(head, choices=[], usage=u)) + "\n\n"
                 yield "data: [DONE]\n\n"
 
@@ -275,8 +281,7 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
             reason = r or reason
         return {"id": rid, "object": "chat.completion", "created": created, "model": served_model_name,
                 "choices": [{"index": 0, "message": {"role": "assistant", "content": text}, "finish_reason": reason}],
-                "usage": {"prompt_tokens": len(ids), "completion_tokens": len(req.output_ids),
-                          "total_tokens": len(ids) + len(req.output_ids)}}
+                "usage": _usage(len(ids), len(req.output_ids), [req])}
 
     @app.get("/metrics")
     async def metrics():
@@ -294,6 +299,13 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
         g("dstack_serving_prompt_tokens_total", "prompt tokens received", state["prompt_tokens"], "counter")
         g("dstack_serving_generation_tokens_total", "tokens generated", state["gen_tokens"], "counter")
         g("dstack_serving_preemptions_total", "sequences preempted (recomputed)", m["preemptions"], "counter")
+        if engine.prefix_caching:
+            g("dstack_serving_prefix_cache_hit_tokens_total", "prompt tokens served from the prefix cache",
+              m["prefix_hit_tokens"], "counter")
+            g("dstack_serving_prefix_cache_query_tokens_total", "prompt tokens looked up in the prefix cache",
+              m["prefix_query_tokens"], "counter")
+            g("dstack_serving_prefix_cached_pages", "KV-cache pages registered for prefix reuse (64 tokens each)",
+              m["prefix_cached_pages"])
         ttft = state["ttft_sum"] / state["ttft_n"] if state["ttft_n"] else 0.0
         g("dstack_serving_ttft_mean_seconds", "mean time to first token", round(ttft, 6))
         return PlainTextResponse("\n".join(lines) + "\n")
