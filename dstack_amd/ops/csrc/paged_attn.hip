@@ -6,15 +6,12 @@
 // KV cache layout, one pair of tensors per layer (PAGE = 64 tokens, head_dim 128):
 //   k_cache [num_pages][KVH][PAGE][128]   token-major: one 256-B row per key
 //   v_cache [num_pages][KVH][128][PAGE]   dim-major:   each V column is a 128-B run of 64 keys
-// so every MFMA operand of the decode kernel is one 16-byte load straight from HBM (no LDS):
+// so every MFMA operand of the attention kernels is one 16-byte load straight from HBM (no LDS);
+// the page walk itself (paged_frag.h: walk_pages) is shared with the prefill kernel.  Decode:
 //
 //  * S^T = K · Q^T with v_mfma_f32_16x16x32_bf16: A = 16 keys x 32 dims (lane = key row, 16 B of
 //    its 256-B row), B = Q^T (lane = query column: the <=16 query heads that share one KV head,
-//    GQA), so one lane holds 4 keys' scores of ONE query -> the softmax max/sum are 16 in-register
-//    ops plus two xor-shuffles (lanes q, q+16, q+32, q+48).
-//  * The 4 key tiles of a page are ordered so that the S^T accumulators, packed to bf16, are
-//    directly the B operand of O^T += V^T · P^T with the keys in natural order (element j of lane
-//    group g = key 32m + 8g + j), and the V^T operand is one 16-B load of the dim-major V page.
+//    GQA), one tile of 16 columns per wave.
 //  * O^T's layout puts the query on the lane, so the online-softmax rescale is lane-local.
 //  * Split-KV: grid = (splits, KVH, batch); each one-wave workgroup walks `pages_per_split` pages,
 //    writes a normalised partial O and its log2-sum-exp, and a combine kernel merges the splits
@@ -23,8 +20,6 @@
 //    hipGraph.
 #include "common.h"
 #include "paged_frag.h"
-
-#include <type_traits>
 
 using namespace dsa;
 using namespace dsa::paged;
@@ -35,6 +30,13 @@ namespace {
 __device__ __forceinline__ unsigned char to_fp8(float x) {
   x = __builtin_amdgcn_fmed3f(x, 448.f, -448.f);
   return (unsigned char)(__builtin_amdgcn_cvt_pk_fp8_f32(x, x, 0, false) & 0xff);
+}
+
+// four floats, each times s -> one word of four e4m3 bytes (x[0] in the low byte, saturating)
+__device__ __forceinline__ unsigned int to_fp8x4(const float* x, float s) {
+  auto sat = [s](float v) { return __builtin_amdgcn_fmed3f(v * s, 448.f, -448.f); };
+  const int w = __builtin_amdgcn_cvt_pk_fp8_f32(sat(x[0]), sat(x[1]), 0, false);
+  return __builtin_amdgcn_cvt_pk_fp8_f32(sat(x[2]), sat(x[3]), w, true);
 }
 
 }  // namespace
@@ -116,30 +118,13 @@ __global__ __launch_bounds__(256) void rope_cache_write_kernel(bf16_t* __restric
     if (head < H || slot < 0) continue;
     const int page = slot / PAGE, off = slot % PAGE;
     if constexpr (FP8) {
-      typedef unsigned int u2 __attribute__((ext_vector_type(2)));
       if (head < H + KVH) {
         unsigned char* dst = (unsigned char*)k_cache + (((size_t)page * KVH + (head - H)) * PAGE + off) * HDIM;
         float x[8], y[8];
         unpack8(a, x);
         unpack8(b, y);
-        u2 wa, wb;
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-          int w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(x[4 * h2] * inv_ks, 448.f, -448.f),
-                                                  __builtin_amdgcn_fmed3f(x[4 * h2 + 1] * inv_ks, 448.f, -448.f), 0,
-                                                  false);
-          wa[h2] = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(x[4 * h2 + 2] * inv_ks, 448.f, -448.f),
-                                                   __builtin_amdgcn_fmed3f(x[4 * h2 + 3] * inv_ks, 448.f, -448.f), w,
-                                                   true);
-          w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(y[4 * h2] * inv_ks, 448.f, -448.f),
-                                              __builtin_amdgcn_fmed3f(y[4 * h2 + 1] * inv_ks, 448.f, -448.f), 0,
-                                              false);
-          wb[h2] = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(y[4 * h2 + 2] * inv_ks, 448.f, -448.f),
-                                                   __builtin_amdgcn_fmed3f(y[4 * h2 + 3] * inv_ks, 448.f, -448.f), w,
-                                                   true);
-        }
-        *reinterpret_cast<u2*>(dst + c * 8) = wa;
-        *reinterpret_cast<u2*>(dst + half + c * 8) = wb;
+        *reinterpret_cast<u2_t*>(dst + c * 8) = u2_t{to_fp8x4(x, inv_ks), to_fp8x4(x + 4, inv_ks)};
+        *reinterpret_cast<u2_t*>(dst + half + c * 8) = u2_t{to_fp8x4(y, inv_ks), to_fp8x4(y + 4, inv_ks)};
       } else {
         unsigned char* dst =
             (unsigned char*)v_cache + ((size_t)page * KVH + (head - H - KVH)) * HDIM * PAGE + off;
@@ -192,153 +177,38 @@ __global__ __launch_bounds__(64) void paged_decode_kernel(
   const int h = kvh * G + qc;
   const bool qvalid = qc < G;
 
-  float m = -INFINITY, l = 0.f;
-  f32x4_t acc[8];
+  float m[1] = {-INFINITY}, l[1] = {0.f};
+  f32x4_t acc[1][8];
 #pragma unroll
-  for (int n = 0; n < 8; ++n) acc[n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  for (int n = 0; n < 8; ++n) acc[0][n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   if (p0 < p1) {
     // Q^T operand: lane (qc, g) holds q[h][32kk + 8g .. +8] for k-step kk
-    bf16x8_t qf[4];
+    bf16x8_t qf[1][4];
     const bf16_t* qrow = q + (long)b * q_stride + (long)(qvalid ? h : kvh * G) * HDIM;
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-      qf[kk] = ld8(qrow + 32 * kk + 8 * g);
-      if (!qvalid) qf[kk] = bf16x8_t{};
+      qf[0][kk] = ld8(qrow + 32 * kk + 8 * g);
+      if (!qvalid) qf[0][kk] = bf16x8_t{};
     }
-    const int* bt = block_tables + (long)b * bt_stride;
-    const int r = lane & 15;
-    // K row offsets of the 4 S^T tiles (key 32(t>>1) + 8(r>>2) + 4(t&1) + (r&3)) and the V^T
-    // fragment offset are lane constants; one page = 16 K + 16 V 16-byte loads per lane.
-    // Two-stage software pipeline, pinned with sched_barrier (left alone, hipcc interleaved
-    // load -> wait -> MFMA with <= 3 loads in flight, which made the kernel latency-bound at
-    // ~1.8 TB/s): V(p) is in flight during S(p) = K(p) Q^T, and K(p+1) during softmax + P V(p).
-    int koff[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) koff[t] = (32 * (t >> 1) + 8 * (r >> 2) + 4 * (t & 1) + (r & 3)) * HDIM + 8 * g;
-    const int voff = r * PAGE + 8 * g;
-    // operands in flight: bf16x8 (16 B) per lane, or the raw 8 e4m3 bytes of an fp8 cache
-    using OpT = typename std::conditional<FP8, u2_t, bf16x8_t>::type;
-    OpT kf[4][4], vf[2][8];
-    auto op = [](const OpT& v) -> bf16x8_t {
-      if constexpr (FP8)
-        return fp8x8_to_bf16(v);
-      else
-        return v;
-    };
-    auto load_k = [&](long page) {
-      if constexpr (FP8) {
-        const unsigned char* kb = (const unsigned char*)k_cache + (page * KVH + kvh) * (long)(PAGE * HDIM);
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) kf[t][kk] = *reinterpret_cast<const u2_t*>(kb + koff[t] + 32 * kk);
-      } else {
-        const bf16_t* kb = (const bf16_t*)k_cache + (page * KVH + kvh) * (long)(PAGE * HDIM);
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) kf[t][kk] = ld8(kb + koff[t] + 32 * kk);
-      }
-    };
-    auto load_v = [&](long page) {
-      if constexpr (FP8) {
-        const unsigned char* vb = (const unsigned char*)v_cache + (page * KVH + kvh) * (long)(PAGE * HDIM);
-#pragma unroll
-        for (int mm = 0; mm < 2; ++mm)
-#pragma unroll
-          for (int n = 0; n < 8; ++n) vf[mm][n] = *reinterpret_cast<const u2_t*>(vb + voff + 16 * n * PAGE + 32 * mm);
-      } else {
-        const bf16_t* vb = (const bf16_t*)v_cache + (page * KVH + kvh) * (long)(PAGE * HDIM);
-#pragma unroll
-        for (int mm = 0; mm < 2; ++mm)
-#pragma unroll
-          for (int n = 0; n < 8; ++n) vf[mm][n] = ld8(vb + voff + 16 * n * PAGE + 32 * mm);
-      }
-    };
-    long page = bt[p0];
-    load_k(page);
-    for (int p = p0; p < p1; ++p) {
-      const long next = p + 1 < p1 ? bt[p + 1] : page;
-      load_v(page);
-      __builtin_amdgcn_sched_barrier(0);
-      // S^T tiles: lane holds keys 32(t>>1) + 8g + 4(t&1) + i, i = 0..3, of query qc
-      f32x4_t s[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        s[t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) s[t] = mfma16(op(kf[t][kk]), qf[kk], s[t]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      load_k(next);  // unconditional (last page: a redundant reload) so vmcnt counting stays static
-      __builtin_amdgcn_sched_barrier(0);
-      page = next;
-      const int base = p * PAGE;
-      float mx = -INFINITY;
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int key = base + 32 * (t >> 1) + 8 * g + 4 * (t & 1) + i;
-          const float v = key < ctx ? s[t][i] * scale_log2 : -INFINITY;
-          s[t][i] = v;
-          mx = fmaxf(mx, v);
-        }
-      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      const float mn = fmaxf(m, mx);
-      const float alpha = fexp2(m - mn);
-      m = mn;
-      float ls = 0.f;
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float e = fexp2(s[t][i] - mn);
-          s[t][i] = e;
-          ls += e;
-        }
-      l = l * alpha + ls;
-#pragma unroll
-      for (int n = 0; n < 8; ++n) acc[n] *= alpha;
-      // P^T operand of PV step mm: element j of lane group g = key 32mm + 8g + j
-#pragma unroll
-      for (int mm = 0; mm < 2; ++mm) {
-        bf16x8_t pf;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          pf[i] = (__bf16)s[2 * mm][i];
-          pf[4 + i] = (__bf16)s[2 * mm + 1][i];
-        }
-#pragma unroll
-        for (int n = 0; n < 8; ++n) acc[n] = mfma16(op(vf[mm][n]), pf, acc[n]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    walk_pages<1, FP8>(k_cache, v_cache, block_tables + (long)b * bt_stride, p0, p1, KVH, kvh, lane, qf,
+                       scale_log2, [&](int, int key) { return key < ctx; }, m, l, acc);
   }
   // O^T accumulator: lane (qc, g) holds O[h][16n + 4g + i]
-  l += __shfl_xor(l, 16, 64);
-  l += __shfl_xor(l, 32, 64);
+  float ls = l[0];
+  ls += __shfl_xor(ls, 16, 64);
+  ls += __shfl_xor(ls, 32, 64);
   if (!qvalid) return;
-  const float inv = l > 0.f ? v_scale / l : 0.f;
+  const float inv = ls > 0.f ? v_scale / ls : 0.f;
   if (DIRECT) {
-    bf16_t* o = out + (long)b * H * HDIM + (long)h * HDIM;
-#pragma unroll
-    for (int n = 0; n < 8; ++n) {
-      typedef unsigned short us4 __attribute__((ext_vector_type(4)));
-      us4 v;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = f2bf(acc[n][i] * inv);
-      *reinterpret_cast<us4*>(o + 16 * n + 4 * g) = v;
-    }
+    store_o_bf16(out + (long)b * H * HDIM + (long)h * HDIM, acc[0], inv, g);
   } else {
     const long idx = ((long)b * H + h) * nsplit + split;
-    if (g == 0) lse_part[idx] = l > 0.f ? m + __log2f(l) : -INFINITY;
-    if (l > 0.f) {  // an empty split writes only its -inf lse; the combine never reads its o
+    if (g == 0) lse_part[idx] = ls > 0.f ? m[0] + __log2f(ls) : -INFINITY;
+    if (ls > 0.f) {  // an empty split writes only its -inf lse; the combine never reads its o
       float* o = o_part + idx * HDIM;
 #pragma unroll
-      for (int n = 0; n < 8; ++n) *reinterpret_cast<f32x4_t*>(o + 16 * n + 4 * g) = acc[n] * inv;
+      for (int n = 0; n < 8; ++n) *reinterpret_cast<f32x4_t*>(o + 16 * n + 4 * g) = acc[0][n] * inv;
     }
   }
 }
@@ -391,7 +261,6 @@ __global__ __launch_bounds__(256) void paged_combine_kernel(const float* __restr
       dsum += red_den[k];
     }
     const float inv = dsum > 0.f ? 1.f / dsum : 0.f;
-    typedef unsigned short us4 __attribute__((ext_vector_type(4)));
     us4 v;
 #pragma unroll
     for (int i = 0; i < 4; ++i) v[i] = f2bf(n[i] * inv);

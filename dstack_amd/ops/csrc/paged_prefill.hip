@@ -5,9 +5,10 @@
 // come from the cache, the chunk's own tokens included (rope_cache_write has stored them on the
 // same stream), so there is one operand path and `start` need not be a page multiple.
 //
-// The MFMA operand scheme is the decode kernel's (paged_attn.hip: S^T = K Q^T, O^T += V^T P^T,
-// every operand one 16-byte load of the cache, no LDS), with the 16 query columns of a tile being
-// 16 consecutive tokens of ONE query head instead of the <= 16 heads of one token:
+// The MFMA operand scheme and the page walk are shared with the decode kernel (paged_frag.h:
+// walk_pages; S^T = K Q^T, O^T += V^T P^T, every operand one 16-byte load of the cache, no LDS),
+// with the 16 query columns of a tile being 16 consecutive tokens of ONE query head instead of the
+// <= 16 heads of one token:
 //
 //  * one wave = (segment, NT column tiles = 16 NT consecutive tokens, one query head): every K
 //    and V fragment it loads is used by NT MFMAs -- the decode form would re-read the prefix once
@@ -23,8 +24,6 @@
 //    tiles (late tokens: most pages) are dealt first.
 #include "common.h"
 #include "paged_frag.h"
-
-#include <type_traits>
 
 using namespace dsa;
 using namespace dsa::paged;
@@ -90,128 +89,9 @@ __global__ __launch_bounds__(64 * MAX_WAVES) void paged_prefill_kernel(
       qf[c][kk] = valid[c] ? ld8(qrow + 32 * kk + 8 * g) : bf16x8_t{};
     }
   }
-  const int* bt = block_tables + (long)seg * bt_stride;
-  const int r = lane & 15;
-  // K row offsets of the 4 S^T tiles (key 32(t>>1) + 8(r>>2) + 4(t&1) + (r&3)) and the V^T fragment
-  // offset are lane constants; one page = 16 K + 16 V 16-byte loads per lane, each feeding NT MFMAs.
-  // The two-stage software pipeline and its sched_barrier placement are the decode kernel's (see
-  // the comment there): V(p) is in flight during S(p), K(p+1) during softmax + P V(p).
-  int koff[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) koff[t] = (32 * (t >> 1) + 8 * (r >> 2) + 4 * (t & 1) + (r & 3)) * HDIM + 8 * g;
-  const int voff = r * PAGE + 8 * g;
-  using OpT = typename std::conditional<FP8, u2_t, bf16x8_t>::type;
-  OpT kf[4][4], vf[2][8];
-  auto op = [](const OpT& v) -> bf16x8_t {
-    if constexpr (FP8)
-      return fp8x8_to_bf16(v);
-    else
-      return v;
-  };
-  auto load_k = [&](long page) {
-    if constexpr (FP8) {
-      const unsigned char* kb = (const unsigned char*)k_cache + (page * KVH + kvh) * (long)(PAGE * HDIM);
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) kf[t][kk] = *reinterpret_cast<const u2_t*>(kb + koff[t] + 32 * kk);
-    } else {
-      const bf16_t* kb = (const bf16_t*)k_cache + (page * KVH + kvh) * (long)(PAGE * HDIM);
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) kf[t][kk] = ld8(kb + koff[t] + 32 * kk);
-    }
-  };
-  auto load_v = [&](long page) {
-    if constexpr (FP8) {
-      const unsigned char* vb = (const unsigned char*)v_cache + (page * KVH + kvh) * (long)(PAGE * HDIM);
-#pragma unroll
-      for (int mm = 0; mm < 2; ++mm)
-#pragma unroll
-        for (int n = 0; n < 8; ++n) vf[mm][n] = *reinterpret_cast<const u2_t*>(vb + voff + 16 * n * PAGE + 32 * mm);
-    } else {
-      const bf16_t* vb = (const bf16_t*)v_cache + (page * KVH + kvh) * (long)(PAGE * HDIM);
-#pragma unroll
-      for (int mm = 0; mm < 2; ++mm)
-#pragma unroll
-        for (int n = 0; n < 8; ++n) vf[mm][n] = ld8(vb + voff + 16 * n * PAGE + 32 * mm);
-    }
-  };
-  long page = bt[0];
-  load_k(page);
-  for (int p = 0; p < p1; ++p) {
-    const long next = p + 1 < p1 ? bt[p + 1] : page;
-    load_v(page);
-    __builtin_amdgcn_sched_barrier(0);
-    // S^T tiles: lane holds keys 32(t>>1) + 8g + 4(t&1) + i, i = 0..3, of column qc of tile c
-    f32x4_t s[NT][4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-#pragma unroll
-      for (int c = 0; c < NT; ++c) s[c][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const bf16x8_t kop = op(kf[t][kk]);
-#pragma unroll
-        for (int c = 0; c < NT; ++c) s[c][t] = mfma16(kop, qf[c][kk], s[c][t]);
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    load_k(next);  // unconditional (last page: a redundant reload) so vmcnt counting stays static
-    __builtin_amdgcn_sched_barrier(0);
-    page = next;
-    const int base = p * PAGE;
-    bf16x8_t pf[NT][2];
-#pragma unroll
-    for (int c = 0; c < NT; ++c) {
-      float mx = -INFINITY;
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int key = base + 32 * (t >> 1) + 8 * g + 4 * (t & 1) + i;
-          const float v = key <= limit[c] ? s[c][t][i] * scale_log2 : -INFINITY;
-          s[c][t][i] = v;
-          mx = fmaxf(mx, v);
-        }
-      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      // key 0 <= limit on the first page, so mn is finite from there on
-      const float mn = fmaxf(m[c], mx);
-      const float alpha = fexp2(m[c] - mn);
-      m[c] = mn;
-      float ls = 0.f;
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const float e = fexp2(s[c][t][i] - mn);
-          s[c][t][i] = e;
-          ls += e;
-        }
-      l[c] = l[c] * alpha + ls;
-#pragma unroll
-      for (int n = 0; n < 8; ++n) acc[c][n] *= alpha;
-      // P^T operand of PV step mm: element j of lane group g = key 32mm + 8g + j
-#pragma unroll
-      for (int mm = 0; mm < 2; ++mm)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          pf[c][mm][i] = (__bf16)s[c][2 * mm][i];
-          pf[c][mm][4 + i] = (__bf16)s[c][2 * mm + 1][i];
-        }
-    }
-#pragma unroll
-    for (int mm = 0; mm < 2; ++mm)
-#pragma unroll
-      for (int n = 0; n < 8; ++n) {
-        const bf16x8_t vop = op(vf[mm][n]);
-#pragma unroll
-        for (int c = 0; c < NT; ++c) acc[c][n] = mfma16(vop, pf[c][mm], acc[c][n]);
-      }
-    __builtin_amdgcn_sched_barrier(0);
-  }
+  // each K and V fragment of a page feeds NT MFMAs; column c attends to keys 0 .. limit[c]
+  walk_pages<NT, FP8>(k_cache, v_cache, block_tables + (long)seg * bt_stride, 0, p1, KVH, kvh, lane, qf, scale_log2,
+                      [&](int c, int key) { return key <= limit[c]; }, m, l, acc);
   // O^T accumulator: lane (qc, g) holds O[token][h][16n + 4g + i]
 #pragma unroll
   for (int c = 0; c < NT; ++c) {
@@ -220,15 +100,7 @@ __global__ __launch_bounds__(64 * MAX_WAVES) void paged_prefill_kernel(
     lc += __shfl_xor(lc, 32, 64);
     if (!valid[c]) continue;
     const float inv = lc > 0.f ? v_scale / lc : 0.f;
-    bf16_t* o = out + (row0 + 16 * c + qc) * ((long)H * HDIM) + (long)h * HDIM;
-#pragma unroll
-    for (int n = 0; n < 8; ++n) {
-      typedef unsigned short us4 __attribute__((ext_vector_type(4)));
-      us4 v;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = f2bf(acc[c][n][i] * inv);
-      *reinterpret_cast<us4*>(o + 16 * n + 4 * g) = v;
-    }
+    store_o_bf16(out + (row0 + 16 * c + qc) * ((long)H * HDIM) + (long)h * HDIM, acc[c], inv, g);
   }
 }
 

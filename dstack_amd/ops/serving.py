@@ -122,6 +122,16 @@ def paged_decode(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
     return out
 
 
+def _gather_kv(k_cache, v_cache, table_row, n: int, n_kv_heads: int, k_scale: float, v_scale: float):
+    """The first ``n`` cached keys and values of one block-table row as fp32 [KVH, n, D] (an fp8
+    cache dequantised with its scales; any other cache holds the values themselves)."""
+    pages = table_row[: (n + PAGE - 1) // PAGE].long()
+    ks, vs = (k_scale, v_scale) if _is_fp8(k_cache) else (1.0, 1.0)
+    k = k_cache[pages].float().permute(1, 0, 2, 3).reshape(n_kv_heads, -1, HEAD_DIM)[:, :n] * ks
+    v = v_cache[pages].float().permute(1, 0, 3, 2).reshape(n_kv_heads, -1, HEAD_DIM)[:, :n] * vs
+    return k, v
+
+
 def paged_decode_ref(q, k_cache, v_cache, block_tables, ctx_lens, n_heads, n_kv_heads, k_scale: float = 1.0,
                      v_scale: float = 1.0):
     """fp32 reference: gathers each sequence's pages and runs plain softmax attention."""
@@ -130,10 +140,7 @@ def paged_decode_ref(q, k_cache, v_cache, block_tables, ctx_lens, n_heads, n_kv_
     out = torch.empty(B, n_heads * HEAD_DIM, dtype=torch.float32, device=q.device)
     for b in range(B):
         n = int(ctx_lens[b])
-        pages = block_tables[b, : (n + PAGE - 1) // PAGE].long()
-        ks, vs = (k_scale, v_scale) if _is_fp8(k_cache) else (1.0, 1.0)
-        k = k_cache[pages].float().permute(1, 0, 2, 3).reshape(n_kv_heads, -1, HEAD_DIM)[:, :n] * ks  # [KVH, n, D]
-        v = v_cache[pages].float().permute(1, 0, 3, 2).reshape(n_kv_heads, -1, HEAD_DIM)[:, :n] * vs
+        k, v = _gather_kv(k_cache, v_cache, block_tables[b], n, n_kv_heads, k_scale, v_scale)
         qb = q[b, : n_heads * HEAD_DIM].float().view(n_kv_heads, G, HEAD_DIM)
         s = torch.einsum("hgd,hnd->hgn", qb, k) / math.sqrt(HEAD_DIM)
         p = torch.softmax(s, dim=-1)
@@ -179,15 +186,12 @@ def paged_prefill_ref(qkv, k_cache, v_cache, block_tables, seg_offsets, seg_star
     Returns [rows, H*128] fp32 with zeros outside the segments."""
     G = n_heads // n_kv_heads
     out = torch.zeros(qkv.shape[0], n_heads * HEAD_DIM, dtype=torch.float32, device=qkv.device)
-    ks, vs = (k_scale, v_scale) if _is_fp8(k_cache) else (1.0, 1.0)
     for s in range(seg_lens.numel()):
         off, start, n = int(seg_offsets[s]), int(seg_starts[s]), int(seg_lens[s])
         if n <= 0:
             continue
         ctx = start + n
-        pages = block_tables[s, : (ctx + PAGE - 1) // PAGE].long()
-        k = k_cache[pages].float().permute(1, 0, 2, 3).reshape(n_kv_heads, -1, HEAD_DIM)[:, :ctx] * ks  # [KVH, ctx, D]
-        v = v_cache[pages].float().permute(1, 0, 3, 2).reshape(n_kv_heads, -1, HEAD_DIM)[:, :ctx] * vs
+        k, v = _gather_kv(k_cache, v_cache, block_tables[s], ctx, n_kv_heads, k_scale, v_scale)
         q = qkv[off : off + n, : n_heads * HEAD_DIM].float().view(n, n_kv_heads, G, HEAD_DIM)
         sc = torch.einsum("ihgd,hkd->hgik", q, k) / math.sqrt(HEAD_DIM)
         key = torch.arange(ctx, device=qkv.device)[None, :]
