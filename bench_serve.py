@@ -45,6 +45,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=3, help="latency mode: requests")
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--temperature", type=float, default=0.0)
+    ap.add_argument("--top-p", type=float, default=1.0, help="nucleus sampling (1 = off)")
+    ap.add_argument("--top-k", type=int, default=0, help="top-k sampling (0 = off)")
+    ap.add_argument("--min-p", type=float, default=0.0, help="min-p sampling (0 = off)")
     ap.add_argument("--quantization", choices=["fp8"], default=None)
     ap.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto")
     ap.add_argument("--enable-prefix-caching", action="store_true",
@@ -74,7 +77,8 @@ def main():
     m = eng.model
     vocab = m.cfg.vocab_size
     rng = np.random.default_rng(0)
-    sp = SamplingParams(max_tokens=args.output_len, temperature=args.temperature, ignore_eos=True)
+    sp = SamplingParams(max_tokens=args.output_len, temperature=args.temperature, top_p=args.top_p, top_k=args.top_k,
+                        min_p=args.min_p, ignore_eos=True)
 
     shared = rng.integers(10, vocab - 10, size=args.shared_prefix_len).tolist() if args.shared_prefix_len else []
 
@@ -113,6 +117,7 @@ def main():
         "kv_cache_dtype": args.kv_cache_dtype, "n_gpus": 1,
         "data": "synthetic prompts (uniform random token ids), random-init weights",
         "num_prompts": n, "input_len": args.input_len, "output_len": args.output_len,
+        "temperature": args.temperature, "top_p": args.top_p, "top_k": args.top_k, "min_p": args.min_p,
         "max_batch": eng.max_batch, "elapsed_s": round(elapsed, 3),
         "output_tokens_per_s": round(out_tokens / elapsed, 1),
         "total_tokens_per_s": round((in_tokens + out_tokens) / elapsed, 1),

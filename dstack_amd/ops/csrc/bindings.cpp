@@ -35,6 +35,13 @@ hipError_t dsa_paged_decode(const void*, long, const void*, const void*, const i
                             float*, int, int, int, int, int, float, int, float, float, hipStream_t);
 hipError_t dsa_sample(const void*, long, int, int, const float*, const int64_t*, const int*, int*, float*,
                       hipStream_t);
+int dsa_top_logprobs_max();
+hipError_t dsa_sample_threshold(const void*, long, int, int, const float*, const int*, const float*, const float*,
+                                float*, hipStream_t);
+hipError_t dsa_sample_masked(const void*, long, int, int, const float*, const int64_t*, const int*, const float*, int*,
+                             float*, hipStream_t);
+hipError_t dsa_top_logprobs(const void*, long, int, int, const float*, const float*, const int*, int*, float*,
+                            hipStream_t);
 hipError_t dsa_paged_prefill(const void*, long, long, const void*, const void*, const int*, int, int, const int*,
                              const int*, const int*, void*, int, int, int, int, float, int, float, float,
                              hipStream_t);
@@ -967,6 +974,75 @@ void sample(torch::Tensor logits, torch::Tensor temps, torch::Tensor seeds, torc
         "sample");
 }
 
+// --- truncated sampling (sampler.hip): every tensor is caller-owned, nothing is allocated or read back ---
+void check_logits(const torch::Tensor& logits) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == torch::kBFloat16 && logits.dim() == 2 &&
+                  logits.stride(1) == 1 && logits.size(1) >= 1,
+              "logits must be bf16 [rows, V >= 1] with contiguous rows");
+}
+
+void check_f32_rows(const torch::Tensor& t, int64_t rows, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.numel() == rows, name,
+              " must be a contiguous fp32 ROCm tensor [rows]");
+}
+
+void check_i32_rows(const torch::Tensor& t, int64_t rows, const char* name) {
+  check_i32(t, name);
+  TORCH_CHECK(t.numel() == rows, name, " must have one entry per row");
+}
+
+// tau (fp32 [rows]) written in place: the smallest logit each row keeps under top-k / top-p / min-p
+void sample_threshold(torch::Tensor logits, torch::Tensor temps, torch::Tensor top_k, torch::Tensor top_p,
+                      torch::Tensor min_p, torch::Tensor tau) {
+  check_logits(logits);
+  const int64_t rows = logits.size(0);
+  check_f32_rows(temps, rows, "temps");
+  check_i32_rows(top_k, rows, "top_k");
+  check_f32_rows(top_p, rows, "top_p");
+  check_f32_rows(min_p, rows, "min_p");
+  check_f32_rows(tau, rows, "tau");
+  check(dsa_sample_threshold(logits.data_ptr(), logits.stride(0), (int)rows, (int)logits.size(1),
+                             temps.data_ptr<float>(), top_k.data_ptr<int>(), top_p.data_ptr<float>(),
+                             min_p.data_ptr<float>(), tau.data_ptr<float>(), stream()),
+        "sample_threshold");
+}
+
+// `sample` over the kept set {x >= tau[r]}
+void sample_masked(torch::Tensor logits, torch::Tensor temps, torch::Tensor seeds, torch::Tensor steps,
+                   torch::Tensor tau, torch::Tensor tokens, torch::Tensor logprobs) {
+  check_logits(logits);
+  const int64_t rows = logits.size(0);
+  check_f32_rows(temps, rows, "temps");
+  TORCH_CHECK(seeds.is_cuda() && seeds.scalar_type() == torch::kInt64 && seeds.numel() == rows &&
+                  seeds.is_contiguous(), "seeds");
+  check_i32_rows(steps, rows, "steps");
+  check_f32_rows(tau, rows, "tau");
+  check_i32_rows(tokens, rows, "tokens");
+  check_f32_rows(logprobs, rows, "logprobs");
+  check(dsa_sample_masked(logits.data_ptr(), logits.stride(0), (int)rows, (int)logits.size(1),
+                          temps.data_ptr<float>(), seeds.data_ptr<int64_t>(), steps.data_ptr<int>(),
+                          tau.data_ptr<float>(), tokens.data_ptr<int>(), logprobs.data_ptr<float>(), stream()),
+        "sample_masked");
+}
+
+// ids (int32) / lps (fp32) [rows, top_logprobs_max] written in place for the rows with top_n > 0
+void top_logprobs(torch::Tensor logits, torch::Tensor temps, torch::Tensor tau, torch::Tensor top_n,
+                  torch::Tensor ids, torch::Tensor lps) {
+  check_logits(logits);
+  const int64_t rows = logits.size(0), N = dsa_top_logprobs_max();
+  check_f32_rows(temps, rows, "temps");
+  check_f32_rows(tau, rows, "tau");
+  check_i32_rows(top_n, rows, "top_n");
+  check_i32(ids, "top_ids");
+  TORCH_CHECK(ids.dim() == 2 && ids.size(0) == rows && ids.size(1) == N, "top_ids must be int32 [rows, ", N, "]");
+  TORCH_CHECK(lps.is_cuda() && lps.scalar_type() == torch::kFloat32 && lps.is_contiguous() && lps.dim() == 2 &&
+                  lps.size(0) == rows && lps.size(1) == N, "top_lps must be fp32 [rows, ", N, "]");
+  check(dsa_top_logprobs(logits.data_ptr(), logits.stride(0), (int)rows, (int)logits.size(1),
+                         temps.data_ptr<float>(), tau.data_ptr<float>(), top_n.data_ptr<int>(), ids.data_ptr<int>(),
+                         lps.data_ptr<float>(), stream()),
+        "top_logprobs");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1045,4 +1121,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("H"), py::arg("KVH"), py::arg("scale"), py::arg("k_scale"), py::arg("v_scale"),
         py::arg("max_len") = -1);
   m.def("sample", &sample);
+  m.def("sample_threshold", &sample_threshold);
+  m.def("sample_masked", &sample_masked);
+  m.def("top_logprobs", &top_logprobs);
+  m.def("top_logprobs_max", &dsa_top_logprobs_max);
 }

@@ -1,7 +1,8 @@
 """Serving ops: paged KV cache writes, paged decode attention, paged-prefix prefill attention and
 sampling.
 
-HIP kernels in ``csrc/paged_attn.hip`` and ``csrc/paged_prefill.hip`` for ROCm tensors; the PyTorch
+HIP kernels in ``csrc/paged_attn.hip``, ``csrc/paged_prefill.hip`` and ``csrc/sampler.hip`` (top-k /
+top-p / min-p truncation, top-N log-probabilities) for ROCm tensors; the PyTorch
 functions here are the CPU path of the engine and the fp32 references the GPU tests compare against.
 
 Cache layout (per layer): ``k_cache [pages, KVH, PAGE, 128]`` token-major and
@@ -239,6 +240,145 @@ def sample_ref(logits, temps, seeds, steps):
     tok = score.argmax(dim=-1)
     lp = z.gather(1, tok[:, None]).squeeze(1) - lse
     return tok.to(torch.int32), lp
+
+
+# ----------------------------------------------------------------------------------------------
+# Truncated sampling (top-k / top-p / min-p) and top-N log-probabilities: csrc/sampler.hip
+# ----------------------------------------------------------------------------------------------
+TOP_LOGPROBS_MAX = 20
+
+
+def sample_threshold(logits: torch.Tensor, temps: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,
+                     min_p: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``tau`` fp32 [R]: row r keeps exactly the logits ``x >= tau[r]``.  Every truncation is a
+    threshold on the logit value, so equal logits are kept or dropped together.  With
+    ``z = x / T`` (``T <= 0``: greedy, z = x) and -inf logits never counted:
+
+    - top-k (``0 < top_k[r] < V``; int32): keep v iff fewer than k tokens are strictly greater than v;
+    - top-p (``top_p[r] < 1``), on the survivors of top-k, with ``w = exp(z - zmax)``: keep v iff the
+      mass of the survivors strictly greater than v is at most p times the survivors' total mass;
+    - min-p (``min_p[r] > 0``): keep v iff ``z >= zmax + ln(min_p)``.
+
+    Each active rule gives the smallest logit of the row that it keeps; ``tau`` is the largest of
+    them, and -inf for a row that asks for nothing (or has no finite logit)."""
+    if out is None:
+        out = torch.empty(logits.shape[0], dtype=torch.float32, device=logits.device)
+    if _ext.use_hip(logits):
+        _ext.require().sample_threshold(logits, temps, top_k, top_p, min_p, out)
+        return out
+    out.copy_(sample_threshold_ref(logits, temps, top_k, top_p, min_p))
+    return out
+
+
+def _inv_temp(temps: torch.Tensor) -> torch.Tensor:
+    """fp32 1/T (1 for greedy rows), as the kernels compute it."""
+    t = temps.float()
+    return torch.where(t > 0, 1.0 / torch.where(t > 0, t, torch.ones_like(t)), torch.ones_like(t))
+
+
+def sample_threshold_ref(logits, temps, top_k, top_p, min_p) -> torch.Tensor:
+    """fp64 reference of :func:`sample_threshold` over each row's distinct values."""
+    R, V = logits.shape
+    x = logits.float().cpu()
+    inv_t = _inv_temp(temps.cpu())
+    ks, ps, ms = top_k.cpu().tolist(), top_p.float().cpu().tolist(), min_p.float().cpu()
+    tau = torch.full((R,), float("-inf"))
+    for r in range(R):
+        k, p, mp = int(ks[r]), max(float(ps[r]), 0.0), float(ms[r])
+        want_k, want_p, want_m = 0 < k < V, p < 1.0, mp > 0.0
+        row = x[r][x[r] > float("-inf")]
+        if not (want_k or want_p or want_m) or row.numel() == 0:
+            continue
+        v, c = torch.unique(row, return_counts=True)
+        v, c = v.flip(0), c.flip(0)  # descending
+        z = (v * inv_t[r]).double()  # (the fp32 product, as the kernel forms it)
+        w = torch.exp(z - z[0]) * c
+        n, cands = v.numel(), []
+        if want_k:
+            n = int(((c.cumsum(0) - c) < k).sum())
+            cands.append(v[n - 1])
+        if want_p:
+            m = w[:n]
+            keep = (m.cumsum(0) - m) <= p * m.sum()
+            cands.append(v[:n][keep][-1])
+        if want_m:
+            cands.append(v[z >= z[0] + math.log(ms[r].double().item())][-1] if mp <= 1.0 else v[0])
+        tau[r] = torch.stack(cands).max()
+    return tau.to(logits.device)
+
+
+def top_logprobs(logits: torch.Tensor, temps: torch.Tensor, tau: torch.Tensor, top_n: torch.Tensor,
+                 top_ids: torch.Tensor | None = None, top_lps: torch.Tensor | None = None):
+    """For rows with ``top_n[r] > 0`` (int32, at most ``TOP_LOGPROBS_MAX``): the kept tokens
+    (``x >= tau[r]``) with the ``top_n`` largest logits, by value descending then token id ascending,
+    as ``top_ids`` int32 / ``top_lps`` fp32 [R, TOP_LOGPROBS_MAX]; ``lp = z - logsumexp(z over the kept
+    set)``, unused entries -1 / -inf.  Rows with ``top_n == 0`` are left as they are."""
+    R = logits.shape[0]
+    if top_ids is None:
+        top_ids = torch.full((R, TOP_LOGPROBS_MAX), -1, dtype=torch.int32, device=logits.device)
+    if top_lps is None:
+        top_lps = torch.full((R, TOP_LOGPROBS_MAX), float("-inf"), dtype=torch.float32, device=logits.device)
+    if _ext.use_hip(logits):
+        _ext.require().top_logprobs(logits, temps, tau, top_n, top_ids, top_lps)
+        return top_ids, top_lps
+    ids, lps = top_logprobs_ref(logits, temps, tau, top_n)
+    rows = top_n > 0
+    top_ids[rows] = ids[rows]
+    top_lps[rows] = lps[rows]
+    return top_ids, top_lps
+
+
+def top_logprobs_ref(logits, temps, tau, top_n):
+    """Reference of :func:`top_logprobs` (fp64 log-sum-exp; a stable sort of -x, so ties go by
+    ascending id).  Rows with ``top_n == 0`` come back as -1 / -inf."""
+    R = logits.shape[0]
+    x = logits.float().cpu()
+    inv_t = _inv_temp(temps.cpu())
+    ids = torch.full((R, TOP_LOGPROBS_MAX), -1, dtype=torch.int32)
+    lps = torch.full((R, TOP_LOGPROBS_MAX), float("-inf"), dtype=torch.float32)
+    for r, n in enumerate(top_n.cpu().tolist()):
+        n = min(int(n), TOP_LOGPROBS_MAX)
+        kept = (x[r] >= tau[r].item()) & (x[r] > float("-inf"))
+        if n <= 0 or not kept.any():
+            continue
+        z = (x[r] * inv_t[r]).double()
+        lse = torch.logsumexp(z[kept], dim=0)
+        order = torch.sort(-x[r], stable=True).indices
+        order = order[kept[order]][:n]
+        ids[r, : order.numel()] = order.to(torch.int32)
+        lps[r, : order.numel()] = (z[order] - lse).float()
+    return ids.to(logits.device), lps.to(logits.device)
+
+
+def sample_filtered(logits: torch.Tensor, temps: torch.Tensor, seeds: torch.Tensor, steps: torch.Tensor,
+                    top_k: torch.Tensor, top_p: torch.Tensor, min_p: torch.Tensor,
+                    tokens: torch.Tensor | None = None, logprobs: torch.Tensor | None = None,
+                    top_n: torch.Tensor | None = None, top_ids: torch.Tensor | None = None,
+                    top_lps: torch.Tensor | None = None, tau: torch.Tensor | None = None):
+    """:func:`sample` over each row's kept set (:func:`sample_threshold`): the same draw per
+    (seed, step, token), restricted to ``x >= tau[r]``, with the chosen token's log-probability under
+    the kept set -- a row that asks for nothing gets what :func:`sample` returns.  With ``top_n``
+    also :func:`top_logprobs` under the same kept set.  On ROCm tensors nothing is allocated when
+    every output (and the ``tau`` workspace) is passed in, so the call can be captured in a hipGraph.
+
+    Returns ``(tokens, logprobs, top_ids, top_lps)``; the last two are None without ``top_n``."""
+    R = logits.shape[0]
+    if tokens is None:
+        tokens = torch.empty(R, dtype=torch.int32, device=logits.device)
+    if logprobs is None:
+        logprobs = torch.empty(R, dtype=torch.float32, device=logits.device)
+    tau = sample_threshold(logits, temps, top_k, top_p, min_p, out=tau)
+    if _ext.use_hip(logits):
+        _ext.require().sample_masked(logits, temps, seeds, steps, tau, tokens, logprobs)
+    else:
+        t, lp = sample_ref(logits.float().masked_fill(logits.float() < tau[:, None], float("-inf")), temps, seeds,
+                           steps)
+        tokens.copy_(t)
+        logprobs.copy_(lp)
+    if top_n is None:
+        return tokens, logprobs, None, None
+    top_ids, top_lps = top_logprobs(logits, temps, tau, top_n, top_ids, top_lps)
+    return tokens, logprobs, top_ids, top_lps
 
 
 # ----------------------------------------------------------------------------------------------

@@ -42,6 +42,8 @@ class SamplingParams:
     temperature: float = 1.0
     top_p: float = 1.0
     top_k: int = 0
+    min_p: float = 0.0  # keep tokens whose probability is at least min_p times the most likely one's
+    top_logprobs: int = 0  # also return the N most likely tokens (<= 20) of every output position
     seed: int | None = None
     ignore_eos: bool = False
     stop_token_ids: tuple = ()
@@ -54,6 +56,7 @@ class Request:
     params: SamplingParams
     output_ids: list = field(default_factory=list)
     logprobs: list = field(default_factory=list)
+    top_logprobs: list = field(default_factory=list)  # per output token: [(token_id, logprob), ...]
     finished: bool = False
     finish_reason: str | None = None
     arrival: float = field(default_factory=time.perf_counter)
@@ -154,14 +157,24 @@ class LLMEngine:
         self.s_steps = torch.zeros(B, **i32)
         self.s_out_tok = torch.zeros(B, **i32)
         self.s_out_lp = torch.zeros(B, dtype=torch.float32, device=dev)
+        # truncation and top-N log-probabilities (padding rows: k = 0, p = 1, min_p = 0, top_n = 0)
+        self.s_top_k = torch.zeros(B, **i32)
+        self.s_top_p = torch.ones(B, dtype=torch.float32, device=dev)
+        self.s_min_p = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.s_top_n = torch.zeros(B, **i32)
+        self.s_tau = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.s_top_ids = torch.full((B, sops.TOP_LOGPROBS_MAX), -1, **i32)
+        self.s_top_lps = torch.full((B, sops.TOP_LOGPROBS_MAX), float("-inf"), dtype=torch.float32, device=dev)
+        self._filter_rows_set = 0  # leading rows of the four parameter buffers that may hold a request's values
         self._ws = {b: sops.DecodeWorkspace(b, self.model.H, self.model.KVH, W, dev) for b in self.buckets}
-        self.s_logits = None  # last decode logits (graph output) for top-k/top-p re-sampling
 
     def _decode_body(self, b: int):
         logits = self.model.decode(self.s_tokens[:b], self.s_pos[:b], self.s_slots[:b], self.s_tables[:b],
                                    self.s_ctx[:b], ws=self._ws[b])
-        sops.sample(logits, self.s_temps[:b], self.s_seeds[:b], self.s_steps[:b], self.s_out_tok[:b],
-                    self.s_out_lp[:b])
+        sops.sample_filtered(logits, self.s_temps[:b], self.s_seeds[:b], self.s_steps[:b], self.s_top_k[:b],
+                             self.s_top_p[:b], self.s_min_p[:b], self.s_out_tok[:b], self.s_out_lp[:b],
+                             top_n=self.s_top_n[:b], top_ids=self.s_top_ids[:b], top_lps=self.s_top_lps[:b],
+                             tau=self.s_tau[:b])
         return logits
 
     def capture_graphs(self):
@@ -171,6 +184,11 @@ class LLMEngine:
         self.s_slots.fill_(-1)
         self.s_ctx.zero_()
         self.s_temps.zero_()
+        self.s_top_k.zero_()
+        self.s_top_p.fill_(1.0)
+        self.s_min_p.zero_()
+        self.s_top_n.zero_()
+        self._filter_rows_set = 0
         torch.cuda.synchronize(self.device)
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
@@ -200,6 +218,10 @@ class LLMEngine:
         vocab = self.model.cfg.vocab_size
         if min(prompt_ids) < 0 or max(prompt_ids) >= vocab:
             raise ValueError(f"token ids must be in [0, {vocab})")
+        if not 0.0 <= params.min_p <= 1.0:
+            raise ValueError(f"min_p must be in [0, 1], got {params.min_p}")
+        if not 0 <= params.top_logprobs <= sops.TOP_LOGPROBS_MAX:
+            raise ValueError(f"top_logprobs must be in [0, {sops.TOP_LOGPROBS_MAX}], got {params.top_logprobs}")
         rid = next(self._ids)
         seed = params.seed if params.seed is not None else (rid * 7919 + 17)
         req = Request(rid, list(prompt_ids), params, on_event=on_event, seed=int(seed))
@@ -267,27 +289,29 @@ class LLMEngine:
                                         torch.from_numpy(plan["slots"]).to(dev), plan["offsets"], plan["lens"],
                                         **(dict(starts=plan["starts"], block_tables=plan["block_tables"])
                                            if self.prefix_caching else {}))
-            tokens, lps = self._sample(logits, reqs)
+            tokens, lps, tops = self._sample(logits, reqs)
             self.stats["prefill_tokens"] += int(sum(plan["lens"]))
             if self.prefix_caching:
                 self.stats.update(prefix_hit_tokens=self.sched.prefix_hit_tokens,
                                   prefix_query_tokens=self.sched.prefix_query_tokens)
             self.stats["prefill_s"] += time.perf_counter() - t0
         else:
-            tokens, lps = self._decode(plan, reqs)
+            tokens, lps, tops = self._decode(plan, reqs)
             self.stats["decode_tokens"] += len(reqs)
             self.stats["decode_s"] += time.perf_counter() - t0
         self.stats["steps"] += 1
         if self.prefix_caching:
             self.stats["prefix_cached_pages"] = self.sched.cached_pages
         now = time.perf_counter()
-        for req, tok, lp in zip(reqs, tokens, lps):
+        for i, (req, tok, lp) in enumerate(zip(reqs, tokens, lps)):
             self.sched.mark_computed(req.id)
             if req.finished:  # aborted while the step ran
                 continue
             tok = int(tok)
             req.output_ids.append(tok)
             req.logprobs.append(float(lp))
+            if req.params.top_logprobs > 0:
+                req.top_logprobs.append([(t, l) for t, l in zip(tops[0][i], tops[1][i]) if t >= 0])
             if req.first_token_at is None:
                 req.first_token_at = now
             if self.prefix_caching:
@@ -315,11 +339,43 @@ class LLMEngine:
         steps = torch.tensor([len(r.output_ids) for r in reqs], dtype=torch.int32)
         return temps, seeds, steps
 
+    def _filter_rows(self, reqs, rows: int | None = None):
+        """top_k, top_p, min_p, top_n of the requests, padded with inert rows up to ``rows``."""
+        pad = max(0, (rows or 0) - len(reqs))
+        top_k = torch.tensor([r.params.top_k for r in reqs] + [0] * pad, dtype=torch.int32)
+        top_p = torch.tensor([r.params.top_p for r in reqs] + [1.0] * pad, dtype=torch.float32)
+        min_p = torch.tensor([r.params.min_p for r in reqs] + [0.0] * pad, dtype=torch.float32)
+        top_n = torch.tensor([r.params.top_logprobs for r in reqs] + [0] * pad, dtype=torch.int32)
+        return top_k, top_p, min_p, top_n
+
+    def _stage_filters(self, reqs, b: int):
+        """Stage truncation / top-N parameters into the static buffers.  Steps where no request asks
+        for any (the common case) touch nothing: the buffers already hold inert rows."""
+        p = [r.params for r in reqs]
+        if any(q.top_k > 0 or q.top_p < 1.0 or q.min_p > 0.0 or q.top_logprobs > 0 for q in p):
+            m = max(b, self._filter_rows_set)
+            for buf, host in zip((self.s_top_k, self.s_top_p, self.s_min_p, self.s_top_n), self._filter_rows(reqs, m)):
+                buf[:m].copy_(host, non_blocking=True)
+            self._filter_rows_set = len(reqs)
+        elif self._filter_rows_set:
+            m, self._filter_rows_set = self._filter_rows_set, 0
+            self.s_top_k[:m].zero_()
+            self.s_top_p[:m].fill_(1.0)
+            self.s_min_p[:m].zero_()
+            self.s_top_n[:m].zero_()
+
+    @staticmethod
+    def _tops(reqs, ids, lps):
+        """The top-N outputs on the host, copied only in steps where some request asked for them."""
+        if not any(r.params.top_logprobs > 0 for r in reqs):
+            return None
+        return ids.tolist(), lps.tolist()
+
     def _sample(self, logits, reqs):
         temps, seeds, steps = (t.to(self.device) for t in self._seed_rows(reqs))
-        logits = _filter_top_k_top_p(logits, reqs)
-        tok, lp = sops.sample(logits, temps, seeds, steps)
-        return tok.tolist(), lp.tolist()
+        top_k, top_p, min_p, top_n = (t.to(self.device) for t in self._filter_rows(reqs))
+        tok, lp, ids, tlp = sops.sample_filtered(logits, temps, seeds, steps, top_k, top_p, min_p, top_n=top_n)
+        return tok.tolist(), lp.tolist(), self._tops(reqs, ids, tlp)
 
     def _decode(self, plan, reqs):
         n = len(reqs)
@@ -337,23 +393,19 @@ class LLMEngine:
             self.s_temps[:n].copy_(temps, non_blocking=True)
             self.s_seeds[:n].copy_(seeds, non_blocking=True)
             self.s_steps[:n].copy_(steps, non_blocking=True)
+            self._stage_filters(reqs, b)
             if b > n:
                 self.s_slots[n:b].fill_(-1)
                 self.s_ctx[n:b].zero_()
                 self.s_temps[n:b].zero_()
-            filtered = any(r.params.top_p < 1.0 or r.params.top_k > 0 for r in reqs)
             if self.tp > 1:
                 self._bcast_decode(b)
             if self._graphs and b in self._graphs:
                 self._graphs[b].replay()
-                logits = self._graph_logits[b]
             else:
-                logits = self._decode_body(b)
-            if filtered:
-                logits = _filter_top_k_top_p(logits[:n], reqs)
-                sops.sample(logits, self.s_temps[:n], self.s_seeds[:n], self.s_steps[:n], self.s_out_tok[:n],
-                            self.s_out_lp[:n])
-            return self.s_out_tok[:n].tolist(), self.s_out_lp[:n].tolist()
+                self._decode_body(b)
+            return (self.s_out_tok[:n].tolist(), self.s_out_lp[:n].tolist(),
+                    self._tops(reqs, self.s_top_ids[:n], self.s_top_lps[:n]))
 
     # ------------------------------------------------------------------------------------------
     # tensor parallel: the leader broadcasts each step's inputs, followers replay them

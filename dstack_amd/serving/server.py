@@ -22,6 +22,7 @@ import uuid
 from fastapi import FastAPI, HTTPException, Request
 from fastapi.responses import JSONResponse, PlainTextResponse, StreamingResponse
 
+from dstack_amd.ops.serving import TOP_LOGPROBS_MAX
 from dstack_amd.serving.engine import LLMEngine, SamplingParams
 from dstack_amd.serving.tokenizer import load_tokenizer
 
@@ -84,7 +85,31 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
             raise HTTPException(404, detail={"message": f"model {name!r} does not exist", "type": "invalid_request_error",
                                              "code": "model_not_found"})
 
-    def _params(body: dict, prompt_len: int, default_max: int) -> SamplingParams:
+    def _bad(msg: str):
+        return HTTPException(400, detail={"message": msg, "type": "invalid_request_error"})
+
+    def _num(body: dict, key: str, kind, default):
+        v = body.get(key)
+        if v is None:
+            return default
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or (kind is int and v != int(v)):
+            raise _bad(f"{key} must be {'an integer' if kind is int else 'a number'}")
+        return kind(v)
+
+    def _top_logprobs(body: dict, chat: bool) -> int:
+        """How many alternatives per position the request asks for: ``logprobs: N`` on
+        /v1/completions, ``logprobs: true`` + ``top_logprobs: N`` on /v1/chat/completions."""
+        if chat:
+            n = _num(body, "top_logprobs", int, 0)
+            if n and not body.get("logprobs"):
+                raise _bad("top_logprobs requires logprobs: true")
+        else:
+            n = 0 if isinstance(body.get("logprobs"), bool) else _num(body, "logprobs", int, 0)
+        if not 0 <= n <= TOP_LOGPROBS_MAX:
+            raise _bad(f"{'top_logprobs' if chat else 'logprobs'} must be between 0 and {TOP_LOGPROBS_MAX}")
+        return n
+
+    def _params(body: dict, prompt_len: int, default_max: int, chat: bool = False) -> SamplingParams:
         max_ctx = engine.model.max_model_len
         if prompt_len >= max_ctx:
             raise HTTPException(400, detail={"message": f"prompt has {prompt_len} tokens; this model's maximum "
@@ -93,8 +118,12 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
         mt = max(1, min(int(mt), max_ctx - prompt_len))
         stop_ids = tuple(body.get("stop_token_ids") or ())
         t = body.get("temperature")
+        min_p = _num(body, "min_p", float, 0.0)
+        if not 0.0 <= min_p <= 1.0:
+            raise _bad("min_p must be between 0 and 1")
         return SamplingParams(max_tokens=mt, temperature=1.0 if t is None else float(t),
                               top_p=float(body.get("top_p") or 1.0), top_k=int(body.get("top_k") or 0),
+                              min_p=min_p, top_logprobs=_top_logprobs(body, chat),
                               seed=body.get("seed"), ignore_eos=bool(body.get("ignore_eos", False)),
                               stop_token_ids=stop_ids)
 
@@ -168,6 +197,19 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
             return p
         raise HTTPException(400, detail={"message": "unsupported prompt format", "type": "invalid_request_error"})
 
+    def _alternatives(req, i):
+        """[(token string, logprob)] of output position i, most likely first."""
+        return [(tok.decode([t]), lp) for t, lp in req.top_logprobs[i]] if req.params.top_logprobs else []
+
+    def _chat_logprob(req, i):
+        """OpenAI's ``choices[].logprobs.content[]`` entry of output position i."""
+        def entry(text, lp):
+            return {"token": text, "logprob": lp, "bytes": list(text.encode("utf-8"))}
+
+        e = entry(tok.decode([req.output_ids[i]]), req.logprobs[i])
+        e["top_logprobs"] = [entry(text, lp) for text, lp in _alternatives(req, i)]
+        return e
+
     def _stop(body):
         s = body.get("stop")
         return [s] if isinstance(s, str) else list(s or [])
@@ -238,6 +280,13 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
                 lp = None
                 if want_lp:
                     lp = {"tokens": [tok.decode([t]) for t in req.output_ids], "token_logprobs": list(req.logprobs)}
+                    if req.params.top_logprobs:
+                        lp["top_logprobs"] = []
+                        for i in range(len(req.output_ids)):
+                            alts: dict = {}
+                            for alt, v in _alternatives(req, i):
+                                alts.setdefault(alt, v)  # two ids with one string: the likelier one
+                            lp["top_logprobs"].append(alts)
                 choices.append({"index": idx, "text": text, "logprobs": lp, "finish_reason": reason})
                 pt += len(p)
                 ct += len(req.output_ids)
@@ -254,7 +303,8 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
         if not isinstance(msgs, list) or not msgs:
             raise HTTPException(400, detail={"message": "messages must be a non-empty list", "type": "invalid_request_error"})
         ids = tok.encode(tok.apply_chat_template(msgs, add_generation_prompt=True), add_bos=True)
-        params = _params(body, len(ids), engine.model.max_model_len - len(ids))
+        params = _params(body, len(ids), engine.model.max_model_len - len(ids), chat=True)
+        want_lp = bool(body.get("logprobs"))
         req, q, st = _submit(ids, params, _stop(body))
         rid = f"chatcmpl-{uuid.uuid4().hex[:24]}"
         created = int(time.time())
@@ -264,10 +314,14 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
                 head = {"id": rid, "object": "chat.completion.chunk", "created": created, "model": served_model_name}
                 yield "data: " + json.dumps(dict(head, choices=[{"index": 0, "delta": {"role": "assistant", "content": ""},
                                                                 "finish_reason": None}])) + "\n\n"
+                sent = 0  # output positions whose logprob entries went out already
                 async for delta, reason in _drain(req, q, st):
                     d = {"content": delta} if delta else {}
-                    yield "data: " + json.dumps(dict(head, choices=[{"index": 0, "delta": d,
-                                                                    "finish_reason": reason}])) + "\n\n"
+                    ch = {"index": 0, "delta": d, "finish_reason": reason}
+                    if want_lp:  # the tokens pushed since the previous chunk
+                        ch["logprobs"] = {"content": [_chat_logprob(req, i) for i in range(sent, len(st.ids))]}
+                        sent = len(st.ids)
+                    yield "data: " + json.dumps(dict(head, choices=[ch])) + "\n\n"
                 if (body.get("stream_options") or {}).get("include_usage"):
                     u = _usage(len(ids), len(req.output_ids), [req])
                     yield "data: " + json.dumps(dict(head, choices=[], usage=u)) + "\n\n"
@@ -279,8 +333,11 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
         async for delta, r in _drain(req, q, st):
             text += delta
             reason = r or reason
+        choice = {"index": 0, "message": {"role": "assistant", "content": text}, "finish_reason": reason}
+        if want_lp:
+            choice["logprobs"] = {"content": [_chat_logprob(req, i) for i in range(len(st.ids))]}
         return {"id": rid, "object": "chat.completion", "created": created, "model": served_model_name,
-                "choices": [{"index": 0, "message": {"role": "assistant", "content": text}, "finish_reason": reason}],
+                "choices": [choice],
                 "usage": _usage(len(ids), len(req.output_ids), [req])}
 
     @app.get("/metrics")
