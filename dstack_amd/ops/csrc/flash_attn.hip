@@ -22,8 +22,8 @@
 #include "mfma_tiles.h"
 typedef unsigned short us4 __attribute__((ext_vector_type(4)));
 
+#include <algorithm>
 #include <cstdlib>
-#include <mutex>
 #include <string>
 
 using namespace dsa;
@@ -47,11 +47,9 @@ constexpr int HD = 128;          // head dim
 // chains, instead of one read -> lgkmcnt(0) -> MFMA per step (which exposes the LDS latency on
 // every MFMA of the phase): 0.702 vs 0.713 ms at S=8192 over three interleaved same-box runs
 // (tools/gpu_sessions/run_r1ze.sh); DSTACK_AMD_FA_FWD_PF=0 selects the old form.
-// PRIO (A/B, DSTACK_AMD_FA_PRIO): 0 = no priority games; 1 = a wave raises its issue priority
-// (s_setprio) for its MFMA phases, so of the two waves on a SIMD the one with matrix work queues
-// it first and the other's softmax VALU fills the gaps; 2 = the softmax phase gets the priority.
-// Measured (3 interleaved runs, S=8192, profiles/fa_prio_ab_r4r.txt): 0 = 0.641-0.650 ms,
-// 1 = 0.659-0.665, 2 = 0.657-0.658 -- both slower, kept opt-in only.
+// Per-phase priority flips (a wave raising s_setprio for its MFMA phases, or for its softmax phase)
+// measured slower and were removed (3 interleaved runs, S=8192, profiles/fa_prio_ab_r4r.txt: none
+// 0.641-0.650 ms, MFMA phases 0.659-0.665, softmax phase 0.657-0.658).
 // STAG (A/B, DSTACK_AMD_FA_FWD_STAG=1; NW = 8): the two waves sharing a SIMD (w and w + 4) run the
 // same per-tile program in lockstep -- both in S = K·Q^T, then both in the softmax VALU while the
 // matrix pipe idles, then both in P·V.  With STAG the second half (w >= 4) defers each tile's P·V
@@ -62,13 +60,14 @@ constexpr int HD = 128;          // head dim
 // for the lockstep default, identical outputs -- slower, kept opt-in only.  With one barrier per
 // tile the two halves still meet every tile, so the deferred P·V lands on the partner's S phase
 // (matrix beside matrix on one SIMD) instead of beside its softmax.
-// PRIO 3 (DSTACK_AMD_FA_HALF_PRIO=1, also for the 8-wave dK/dV and dQ passes): one s_setprio 1 for
+// HP (DSTACK_AMD_FA_HALF_PRIO=1, also for the 8-wave dK/dV and dQ passes): one s_setprio 1 for
 // waves 4-7 at kernel start, no per-phase flips.  Measured (4 interleaved runs, S=8192,
 // profiles/fa_hprio_ab_r4y.txt): forward 0.656-0.670 vs 0.657-0.668 ms, backward 2.018-2.036 vs
 // 2.009-2.053 ms -- within noise, kept opt-in.
 // BUF (default; DSTACK_AMD_FA_FWD_BUF=0 turns it off): K/V tiles through buffer descriptors (dma_tile64_buf), which keeps
-// the S phase's LDS-read waits counted instead of lgkmcnt(0).
-template <bool CAUSAL, int NW = 4, bool PF = true, int PRIO = 0, bool STAG = false, bool BUF = false, int FPD = 4>
+// the S phase's LDS-read waits counted instead of lgkmcnt(0).  8 instead of 4 S-phase reads in
+// flight measured no gain with it (profiles/fa_pf3_pfd8_ab_r8z.txt) and was removed.
+template <bool CAUSAL, int NW = 4, bool PF = true, bool HP = false, bool STAG = false, bool BUF = false>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void fa_fwd_kernel(const bf16_t* __restrict__ qkv,
                                                         bf16_t* __restrict__ out,
                                                         float* __restrict__ lse, int B, int S,
@@ -88,8 +87,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void fa_fwd_kernel(const 
   const bf16_t* kp = base + (H + kvh) * HD;
   const bf16_t* vp = base + (H + KVH + kvh) * HD;
   const int q0 = qb * QB, qw0 = q0 + 32 * w, myq = qw0 + l32;
-  // PRIO 3: static priority for the second-dispatched half (the arbitration loser of each SIMD pair)
-  if constexpr (PRIO == 3) {
+  // HP: static priority for the second-dispatched half (the arbitration loser of each SIMD pair)
+  if constexpr (HP) {
     if (w >= NW / 2) __builtin_amdgcn_s_setprio(1);
   }
 
@@ -150,10 +149,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void fa_fwd_kernel(const 
       for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) st[t][r] = 0.f;
-      if constexpr (PRIO == 1) __builtin_amdgcn_s_setprio(3);
       if constexpr (PF) {
         // step i: key tile t = i & 1, k-slice ks = i >> 1; fragment i + 4 is read while i computes
-        constexpr int PD = BUF ? FPD : 4;  // reads in flight
+        constexpr int PD = 4;  // reads in flight
         bf16x8 kf[PD];
 #pragma unroll
         for (int i = 0; i < PD; ++i) kf[i] = lds_row(kl, 32 * (i & 1) + l32, 2 * (i >> 1) + hf);
@@ -179,8 +177,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void fa_fwd_kernel(const 
 #pragma unroll
           for (int ks = 0; ks < 8; ++ks) st[t] = mfma(lds_row(kl, 32 * t + l32, 2 * ks + hf), qf[ks], st[t]);
       }
-      if constexpr (PRIO == 1) __builtin_amdgcn_s_setprio(0);
-      if constexpr (PRIO == 2) __builtin_amdgcn_s_setprio(3);
       // only the tile(s) crossing this wave's diagonal need the causal mask (wave-uniform test)
       if (CAUSAL && kv0 + 63 > qw0) {
 #pragma unroll
@@ -223,8 +219,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void fa_fwd_kernel(const 
       bf16x8 pb[4];
 #pragma unroll
       for (int s4 = 0; s4 < 4; ++s4) pb[s4] = to_bf16x8(st[s4 >> 1], 8 * (s4 & 1));
-      if constexpr (PRIO == 2) __builtin_amdgcn_s_setprio(0);
-      if constexpr (PRIO == 1) __builtin_amdgcn_s_setprio(3);
       if (late) {
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4) pbp[s4] = pb[s4];
@@ -235,7 +229,6 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void fa_fwd_kernel(const 
 #pragma unroll
           for (int s4 = 0; s4 < 4; ++s4) o[d] = mfma(lds_tr(vl, 16 * s4, 32 * d, lane), pb[s4], o[d]);
       }
-      if constexpr (PRIO == 1) __builtin_amdgcn_s_setprio(0);
     }
     wait_dma_and_barrier();
   }
@@ -337,13 +330,15 @@ __global__ __launch_bounds__(256) void fa_bwd_delta_tiled_kernel(const bf16_t* _
 // Loops over 64-row q tiles from the diagonal to S; writes fp32 per-q-head partials
 // dkp/dvp [B, S, H, 128] that fa_bwd_reduce_kv sums over the GQA group.
 // ================================================================================================
-template <bool CAUSAL, int NQS>
+template <bool CAUSAL>
 __global__ __launch_bounds__(256, DKDV_WAVES_PER_SIMD) void fa_bwd_dkdv_kernel(
     const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout, const float* __restrict__ lse,
     const float* __restrict__ delta, float* __restrict__ dkp, float* __restrict__ dvp, int B, int S,
     int H, int KVH, float scale_log2) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   // a stage holds QT = 32*NQS query rows: Q (QT x 256 B) | dO (QT x 256 B) | lse (QT x 4) | delta
+  // (128-row stages -- half the barriers, 130 KiB of LDS -- never measured faster and were removed)
+  constexpr int NQS = 2;
   constexpr int QT = 32 * NQS;
   constexpr int QB = QT * 256;
   constexpr int STAGE = 2 * QB + 8 * QT;
@@ -492,8 +487,12 @@ __global__ __launch_bounds__(256, DKDV_WAVES_PER_SIMD) void fa_bwd_dkdv_kernel(
 // P16 (DSTACK_AMD_FA_DKDV_BF16, default on): the per-query-head dK/dV partials go to HBM as bf16 (the
 // layout flash-attention 2 uses for its GQA expansion: per-head bf16 partials, summed in fp32 by the
 // group reduction), halving the 2 x B*S*H*128 partial bytes written here and read back by the reduce.
-template <bool CAUSAL, bool SEED = false, bool HP = false, bool SPILL = false, bool GQA = false, bool TR = false,
-          int PF = 0, bool P16 = false>
+// Rejected and removed: accumulators seeded with the row constants (-lse / scale, -delta) and a
+// 64-keys-per-wave kernel (profiles/fa_dkdv_seed_ab_r4h.txt, whole backward S=8192, 3 interleaved
+// runs: this kernel 675-684 TFLOP/s, seeded 583-592, 64 keys per wave 576-581), and PF 3
+// (profiles/fa_pf3_pfd8_ab_r8z.txt).
+template <bool CAUSAL, bool HP = false, bool SPILL = false, bool GQA = false, bool TR = false, int PF = 0,
+          bool P16 = false>
 __global__ __launch_bounds__(512, 2) void fa_bwd_dkdv8_kernel(
     const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout, const float* __restrict__ lse,
     const float* __restrict__ delta, float* __restrict__ dkp, float* __restrict__ dvp, int B, int S,
@@ -610,21 +609,10 @@ __global__ __launch_bounds__(512, 2) void fa_bwd_dkdv8_kernel(
     const int qlo = qt * 64 + 32 * qh;
     if (!CAUSAL || qlo + 31 >= kw0) {  // some query of my half-tile sees my keys
       f32x16 sc, dpv;
-      // SEED: the row constants start the accumulators (S' = Q.K^T - lse/scale, dP' = dO.V^T -
-      // delta), so p = exp2(scale * S') and dS = p * dP' need no per-element subtractions
 #pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int qi = 32 * qh + 8 * rr + 4 * hf;
-        f4 L = {0.f, 0.f, 0.f, 0.f}, Dl = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (SEED) {
-          L = *reinterpret_cast<const f4*>(ll + qi);
-          Dl = *reinterpret_cast<const f4*>(dl + qi);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          sc[4 * rr + i] = SEED ? -L[i] / scale_log2 : 0.f;
-          dpv[4 * rr + i] = SEED ? -Dl[i] : 0.f;
-        }
+      for (int r = 0; r < 16; ++r) {
+        sc[r] = 0.f;
+        dpv[r] = 0.f;
       }
       if constexpr (PF) {
         // step i: chain i & 1 (0 = S from Q.K^T, 1 = dP from dO.V^T), k-slice i >> 1
@@ -670,11 +658,9 @@ __global__ __launch_bounds__(512, 2) void fa_bwd_dkdv8_kernel(
       // + 16 s_and; the branch costs the other tiles nothing.
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
-        f4 L = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (!SEED) L = *reinterpret_cast<const f4*>(ll + 32 * qh + 8 * rr + 4 * hf);
+        const f4 L = *reinterpret_cast<const f4*>(ll + 32 * qh + 8 * rr + 4 * hf);
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-          sc[4 * rr + i] = SEED ? fexp2(sc[4 * rr + i] * scale_log2) : fexp2(fmaf(sc[4 * rr + i], scale_log2, -L[i]));
+        for (int i = 0; i < 4; ++i) sc[4 * rr + i] = fexp2(fmaf(sc[4 * rr + i], scale_log2, -L[i]));
       }
       if (__builtin_expect(diag, 0)) {
 #pragma unroll
@@ -683,12 +669,11 @@ __global__ __launch_bounds__(512, 2) void fa_bwd_dkdv8_kernel(
       }
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
-        f4 Dl = {0.f, 0.f, 0.f, 0.f};
-        if constexpr (!SEED) Dl = *reinterpret_cast<const f4*>(dl + 32 * qh + 8 * rr + 4 * hf);
+        const f4 Dl = *reinterpret_cast<const f4*>(dl + 32 * qh + 8 * rr + 4 * hf);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int r = 4 * rr + i;
-          dpv[r] = SEED ? sc[r] * dpv[r] : sc[r] * (dpv[r] - Dl[i]);
+          dpv[r] = sc[r] * (dpv[r] - Dl[i]);
         }
       }
       bf16x8 pb[2], dsb[2];
@@ -1037,171 +1022,6 @@ __global__ __launch_bounds__(512, 2) void fa_bwd_dkdv8d_kernel(
         }
         *reinterpret_cast<f4*>(dkp + row + dd) = ok;
         *reinterpret_cast<f4*>(dvp + row + dd) = ov;
-      }
-  }
-}
-
-// ================================================================================================
-// Backward dK/dV pass, 64 keys per wave: workgroup = 4 waves = 256 keys of one (b, q-head), one
-// wave per SIMD.  Each wave keeps K (and, with VREG, V) of its 64 keys in registers and dK^T / dV^T
-// of those keys in 256 accumulator registers, and sweeps 32-query slices of Q/dO staged in LDS:
-// every Q / dO fragment read from LDS (rows for S and dP, transposed for dV^T and dK^T) feeds the
-// MFMAs of TWO 32-key tiles, so a slice costs 32 KiB of LDS reads for 64 MFMAs per wave (the 8-wave
-// kernel above: 48 KiB for 32) -- MFMA-bound instead of LDS-bound.  With VREG = false, V of the
-// block sits in LDS (64 KiB) and is read as the dP B operand, which frees 64 VGPRs.  Same fp32
-// per-q-head partial output as fa_bwd_dkdv_kernel.
-// ================================================================================================
-template <bool CAUSAL, bool VREG>
-__global__ __launch_bounds__(256, 1) void fa_bwd_dkdv64_kernel(
-    const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout, const float* __restrict__ lse,
-    const float* __restrict__ delta, float* __restrict__ dkp, float* __restrict__ dvp, int B, int S,
-    int H, int KVH, float scale_log2) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int STAGE = 2 * TILE_BYTES + 512;         // Q (64 rows) | dO (64 rows) | lse | delta
-  constexpr int V_BYTES = VREG ? 0 : 4 * TILE_BYTES;  // V of the 256 keys (four 64-row tiles)
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, hf = lane >> 5, l32 = lane & 31;
-  const int NH = H + 2 * KVH;
-  const long rs = (long)NH * HD;
-  const long ors = (long)H * HD;
-  const int bid = blockIdx.x;
-  const int kb = bid / (B * H);  // small kb = most q tiles: heaviest first
-  const int bh = bid % (B * H);
-  const int b = bh / H, hh = bh % H, kvh = hh / (H / KVH);
-  const bf16_t* base = qkv + (long)b * S * rs;
-  const bf16_t* qp = base + hh * HD;
-  const bf16_t* kp = base + (H + kvh) * HD;
-  const bf16_t* vp = base + (H + KVH + kvh) * HD;
-  const bf16_t* dop = dout + (long)b * S * ors + hh * HD;
-  const float* lp = lse + ((long)b * H + hh) * S;
-  const float* dp = delta + ((long)b * H + hh) * S;
-  const int kb0 = kb * 256, kw0 = kb0 + 64 * w;
-  char* vl = smem;  // (VREG = false) V rows of the block, 4 x 64-row tiles
-  char* ring = smem + V_BYTES;
-
-  bf16x8 kf[2][8];
-  bf16x8 vf[2][VREG ? 8 : 1];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      kf[t][ks] = *reinterpret_cast<const bf16x8*>(kp + (long)(kw0 + 32 * t + l32) * rs + 16 * ks + 8 * hf);
-      if constexpr (VREG)
-        vf[t][ks] = *reinterpret_cast<const bf16x8*>(vp + (long)(kw0 + 32 * t + l32) * rs + 16 * ks + 8 * hf);
-    }
-  if constexpr (!VREG) {
-#pragma unroll
-    for (int h64 = 0; h64 < 4; ++h64)
-      dma_tile64(vp + (long)(kb0 + 64 * h64) * rs, rs, vl + h64 * TILE_BYTES, w, lane);
-  }
-  f32x16 dk[2][4], dv[2][4];
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        dk[t][d][r] = 0.f;
-        dv[t][d][r] = 0.f;
-      }
-  const int qt_begin = CAUSAL ? kb0 / 64 : 0;
-  const int nqt = S / 64;
-  auto issue = [&](int qt, char* st) {
-    dma_tile64(qp + (long)qt * 64 * rs, rs, st, w, lane);
-    dma_tile64(dop + (long)qt * 64 * ors, ors, st + TILE_BYTES, w, lane);
-    if (w == 0) dma_f32x64(lp + qt * 64, st + 2 * TILE_BYTES, lane);
-    if (w == 1) dma_f32x64(dp + qt * 64, st + 2 * TILE_BYTES + 256, lane);
-  };
-  issue(qt_begin, ring);
-  wait_dma_and_barrier();
-
-  for (int qt = qt_begin; qt < nqt; ++qt) {
-    const int stage = (qt - qt_begin) & 1;
-    const char* ql = ring + stage * STAGE;
-    const char* dol = ql + TILE_BYTES;
-    const float* ll = reinterpret_cast<const float*>(ql + 2 * TILE_BYTES);
-    const float* dl = ll + 64;
-    if (qt + 1 < nqt) issue(qt + 1, ring + (stage ^ 1) * STAGE);
-#pragma unroll 1  // one slice's temporaries live at a time (256 AGPR accumulators + K/V)
-    for (int qs = 0; qs < 2; ++qs) {
-      const int qlo = qt * 64 + 32 * qs;
-      if (CAUSAL && qlo + 31 < kw0) continue;  // every query of the slice precedes my keys
-      f32x16 sc[2], dpv[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          sc[t][r] = 0.f;
-          dpv[t][r] = 0.f;
-        }
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        const bf16x8 aq = lds_row(ql, 32 * qs + l32, 2 * ks + hf);
-        const bf16x8 ad = lds_row(dol, 32 * qs + l32, 2 * ks + hf);
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          sc[t] = mfma(aq, kf[t][ks], sc[t]);
-          if constexpr (VREG)
-            dpv[t] = mfma(ad, vf[t][ks], dpv[t]);
-          else
-            dpv[t] = mfma(ad, lds_row(vl, 64 * w + 32 * t + l32, 2 * ks + hf), dpv[t]);
-        }
-      }
-      // rows of sc/dpv: q = qlo + (r&3) + 8*(r>>2) + 4*hf ; column (lane) = key kw0 + 32t + l32
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int qi = 32 * qs + 8 * rr + 4 * hf;
-        const f4 L = *reinterpret_cast<const f4*>(ll + qi);
-        const f4 Dl = *reinterpret_cast<const f4*>(dl + qi);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int r = 4 * rr + i;
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            float pv = fexp2(fmaf(sc[t][r], scale_log2, -L[i]));
-            if (CAUSAL && qlo < kw0 + 32 * t + 31 && kw0 + 32 * t + l32 > qt * 64 + qi + i) pv = 0.f;
-            sc[t][r] = pv;
-            dpv[t][r] = pv * (dpv[t][r] - Dl[i]);
-          }
-        }
-      }
-      bf16x8 pb[2][2], dsb[2][2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int k2 = 0; k2 < 2; ++k2) {
-          pb[t][k2] = to_bf16x8(sc[t], 8 * k2);
-          dsb[t][k2] = to_bf16x8(dpv[t], 8 * k2);
-        }
-#pragma unroll
-      for (int d = 0; d < 4; ++d)
-#pragma unroll
-        for (int k2 = 0; k2 < 2; ++k2) {
-          const bf16x8 at = lds_tr(dol, 32 * qs + 16 * k2, 32 * d, lane);
-          const bf16x8 qtr = lds_tr(ql, 32 * qs + 16 * k2, 32 * d, lane);
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            dv[t][d] = mfma(at, pb[t][k2], dv[t][d]);
-            dk[t][d] = mfma(qtr, dsb[t][k2], dk[t][d]);
-          }
-        }
-    }
-    wait_dma_and_barrier();
-  }
-  const float sm = scale_log2 * 0.6931471805599453f;  // softmax scale = scale_log2 * ln2
-#pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int key = kw0 + 32 * t + l32;
-    float* dkr = dkp + (((long)b * S + key) * H + hh) * HD;
-    float* dvr = dvp + (((long)b * S + key) * H + hh) * HD;
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const int dd = 32 * d + 8 * rr + 4 * hf;
-        *reinterpret_cast<f4*>(dkr + dd) = f4{dk[t][d][4 * rr] * sm, dk[t][d][4 * rr + 1] * sm,
-                                              dk[t][d][4 * rr + 2] * sm, dk[t][d][4 * rr + 3] * sm};
-        *reinterpret_cast<f4*>(dvr + dd) = f4{dv[t][d][4 * rr], dv[t][d][4 * rr + 1], dv[t][d][4 * rr + 2],
-                                              dv[t][d][4 * rr + 3]};
       }
   }
 }
@@ -1566,110 +1386,263 @@ __global__ __launch_bounds__(64 * NW) void fa_bwd_dq_ds_kernel(const bf16_t* __r
 }
 
 // ================================================================================================
-// launchers
+// launchers: the switches (read once per process), one launch plan per pass (pure host code that
+// decides which instantiation runs and with what geometry), then the launches
 // ================================================================================================
 static inline bool fa_shape_ok(int S, int H, int KVH, int D) {
   return D == HD && S % 128 == 0 && S > 0 && KVH > 0 && H % KVH == 0;
 }
 
+// the value of an environment variable, or dflt when it is unset
+static const char* fa_env(const char* name, const char* dflt) {
+  const char* v = getenv(name);
+  return v ? v : dflt;
+}
+
+// Every DSTACK_AMD_FA_* switch, resolved once per process (fa_sw()).  The default is what measured
+// fastest; the others stay for A/B runs and as the fallbacks of shapes the default does not cover.
+// A value that names a removed variant selects the default.
+struct FaSwitches {
+  // deferred-max threshold (log2 units; 0 = rescale on every new max): 8 takes the S=8192 causal
+  // forward from 0.700 to 0.660 ms, same fp32-reference error (tools/gpu_sessions/run_r2r.sh)
+  float rescale_thr = (float)atof(fa_env("DSTACK_AMD_FA_RESCALE_THR", "8"));
+  // forward: 8 waves (one 256-row workgroup per CU) by default: 0.710 vs 0.720 ms at S=8192, three
+  // interleaved same-box runs (tools/gpu_sessions/run_r1s.sh); 4 selects the 4-wave form
+  int fwd_waves = atoi(fa_env("DSTACK_AMD_FA_FWD_WAVES", "8")) == 4 ? 4 : 8;
+  // forward S phase with 4 K-fragment reads in flight (0 selects read -> wait -> MFMA per step)
+  bool fwd_pf = atoi(fa_env("DSTACK_AMD_FA_FWD_PF", "1")) != 0;
+  // forward with the second half's P.V deferred by one tile (slower: see fa_fwd_kernel's STAG)
+  bool fwd_stag = atoi(fa_env("DSTACK_AMD_FA_FWD_STAG", "0")) == 1;
+  // static priority for waves 4-7 of the 8-wave forward, dK/dV and dQ kernels (within noise: see
+  // fa_fwd_kernel's HP)
+  bool half_prio = atoi(fa_env("DSTACK_AMD_FA_HALF_PRIO", "0")) == 1;
+  // forward K/V through buffer descriptors (0 selects global_load_lds): forward 0.647-0.663 vs
+  // 0.660-0.679 ms, S=8192, 3 interleaved runs (profiles/fa_dq_fwd_ab_r8w.txt)
+  bool fwd_buf = atoi(fa_env("DSTACK_AMD_FA_FWD_BUF", "1")) != 0;
+  // dK/dV kernel: the 8-wave K/V-resident variant is the default (2.10 vs 2.53 ms for the whole
+  // backward at S=8192, same box); DSTACK_AMD_FA_DKDV=4w selects the 4-wave register-resident one
+  bool dkdv_4w = std::string(fa_env("DSTACK_AMD_FA_DKDV", "8w")) == "4w";
+  // GQA-summed dK/dV (one workgroup per KV head and key block, bf16 written directly, no reduce
+  // kernel): DSTACK_AMD_FA_DKDV_GQA=1
+  bool dkdv_gqa = atoi(fa_env("DSTACK_AMD_FA_DKDV_GQA", "0")) == 1;
+  // S/dP read pipeline of the 8-wave dK/dV pass (DSTACK_AMD_FA_DKDV_PF=0|1|2, default 2).  Whole
+  // backward at S=8192, 3 interleaved runs (profiles/fa_bwd_pf_ab_r8t.txt): PF 0 2.031-2.045 ms,
+  // PF 2 1.959-1.963 ms.  The dQ pass's counterpart (DSTACK_AMD_FA_DQ_PF=1|2) measured no gain.
+  int dkdv_pf = [] {
+    const int v = atoi(fa_env("DSTACK_AMD_FA_DKDV_PF", "2"));
+    return v < 0 || v > 2 ? 2 : v;
+  }();
+  // decoupled halves (fa_bwd_dkdv8d_kernel): DSTACK_AMD_FA_DKDV_DEC=1 (2: with the early dV/dK
+  // operand reads), waves 4-7 started DSTACK_AMD_FA_DKDV_STAG x 64 clocks late
+  int dkdv_dec = atoi(fa_env("DSTACK_AMD_FA_DKDV_DEC", "0"));
+  int dkdv_stag = atoi(fa_env("DSTACK_AMD_FA_DKDV_STAG", "0"));
+  // bf16 per-query-head dK/dV partials (DSTACK_AMD_FA_DKDV_BF16=1|0): the default 8-wave PF-2 pass only
+  bool dkdv_bf16 = atoi(fa_env("DSTACK_AMD_FA_DKDV_BF16", "1")) == 1;
+  // dQ pass: 8 waves / 256 query rows per workgroup when S % 256 == 0 (DSTACK_AMD_FA_DQ_WAVES=4|8).
+  // Whole backward at S=8192, same box, 3 interleaved runs each (tools/gpu_sessions/run_r1t.sh): 4 waves 2.06-2.08
+  // ms; 8 waves 2.04-2.07; 8 waves with the dP accumulator seeded with -delta ('row constant')
+  // 2.00-2.05 -- the seeding is kept for 8 waves only: with 4 waves it measured 2.14-2.17 ms.
+  int dq_waves = atoi(fa_env("DSTACK_AMD_FA_DQ_WAVES", "8")) == 4 ? 4 : 8;
+  // dQ pass: DSTACK_AMD_FA_DQ_PF=0|1|2, default 1 (whole backward 1.924-1.946 vs 1.945-1.964 ms;
+  // 2 spills and measured 1.976-2.000, profiles/fa_dq_fwd_ab_r8w.txt)
+  int dq_pf = [] {
+    const int v = atoi(fa_env("DSTACK_AMD_FA_DQ_PF", "1"));
+    return v < 0 ? 0 : (v > 2 ? 2 : v);
+  }();
+  // dS spill for the recompute-free dQ pass (DSTACK_AMD_FA_DQ=ds|recompute): B*H*S*S bf16 of
+  // workspace, used while it stays under DSTACK_AMD_FA_DS_MAX_GB (default 16)
+  bool dq_ds = std::string(fa_env("DSTACK_AMD_FA_DQ", "recompute")) == "ds";
+  double ds_max_gb = atof(fa_env("DSTACK_AMD_FA_DS_MAX_GB", "16"));
+  // Measured, rejected and removed: the dQ pass on a second stream beside the dK/dV pass
+  // (profiles/fa_dq_side_stream_ab_r9m.txt: slower).
+};
+static const FaSwitches& fa_sw() {
+  static const FaSwitches sw;
+  return sw;
+}
+
+// the buffer-descriptor forms address a K/V (or Q / dO) tile with 32-bit byte offsets into qkv
+static inline bool fa_qkv_under_2g(int S, int H, int KVH) { return (long)S * (H + 2 * KVH) * HD * 2 < (1L << 31); }
+
+constexpr size_t FA_LDS_DKDV8 = 2 * 128 * 256 + 2 * (2 * TILE_BYTES + 512);      // K|V + 2 x (Q|dO|lse|delta)
+constexpr size_t FA_LDS_DKDV8D = 2 * 128 * 256 + 4 * (2 * 32 * 256 + 512) + 16;  // K|V + 4 half rings + counters
+
+// ---- forward ------------------------------------------------------------------------------------
+enum class FaFwd { W4, W8, W8_NOPF, W8_HP, W8_STAG, W8_BUF };
+struct FaFwdPlan {
+  FaFwd form;
+  int grid, block;
+  size_t lds;
+};
+// Precedence, first match wins:
+//   DSTACK_AMD_FA_FWD_WAVES=4 or S % 256 != 0   4 waves, 128 query rows per workgroup (prefetched S
+//                                               phase, global_load_lds: no other switch applies)
+//   not causal                                  8 waves, prefetched S phase, global_load_lds
+//   DSTACK_AMD_FA_FWD_PF=0                      8 waves without the S-phase prefetch
+//   DSTACK_AMD_FA_HALF_PRIO=1                   8 waves, static priority for waves 4-7
+//   DSTACK_AMD_FA_FWD_STAG=1                    8 waves, staggered halves, 3-deep K/V ring
+//   default                                     8 waves, K/V through buffer descriptors
+//   DSTACK_AMD_FA_FWD_BUF=0 or qkv >= 2^31 B    8 waves, global_load_lds
+static FaFwdPlan fa_fwd_plan(int B, int S, int H, int KVH, bool causal) {
+  const FaSwitches& sw = fa_sw();
+  FaFwdPlan p;
+  if (sw.fwd_waves == 4 || S % 256 != 0) p.form = FaFwd::W4;
+  else if (!causal) p.form = FaFwd::W8;
+  else if (!sw.fwd_pf) p.form = FaFwd::W8_NOPF;
+  else if (sw.half_prio) p.form = FaFwd::W8_HP;
+  else if (sw.fwd_stag) p.form = FaFwd::W8_STAG;
+  else if (sw.fwd_buf && fa_qkv_under_2g(S, H, KVH)) p.form = FaFwd::W8_BUF;
+  else p.form = FaFwd::W8;
+  const int nw = p.form == FaFwd::W4 ? 4 : 8;
+  p.grid = B * H * (S / (32 * nw));
+  p.block = 64 * nw;
+  p.lds = (p.form == FaFwd::W8_STAG ? 6 : 4) * TILE_BYTES;
+  return p;
+}
+
+using FaFwdKernel = void (*)(const bf16_t*, bf16_t*, float*, int, int, int, int, float, float);
+// the instantiation of a plan; nullptr for a form the pass has no kernel for (fa_fwd_plan gives a
+// non-causal pass W4 or W8 only), which the launcher reports instead of running something else
+template <bool CAUSAL>
+static FaFwdKernel fa_fwd_select(FaFwd form) {
+  if (form == FaFwd::W4) return fa_fwd_kernel<CAUSAL>;
+  if (form == FaFwd::W8) return fa_fwd_kernel<CAUSAL, 8>;
+  if constexpr (CAUSAL) {
+    if (form == FaFwd::W8_NOPF) return fa_fwd_kernel<true, 8, false>;
+    if (form == FaFwd::W8_HP) return fa_fwd_kernel<true, 8, true, true>;
+    if (form == FaFwd::W8_STAG) return fa_fwd_kernel<true, 8, true, false, true>;
+    if (form == FaFwd::W8_BUF) return fa_fwd_kernel<true, 8, true, false, false, true>;
+  }
+  return nullptr;
+}
+
 extern "C" hipError_t dsa_fa_fwd(const void* qkv, void* out, float* lse, int B, int S, int H, int KVH,
                                  int D, float scale, int causal, hipStream_t st) {
   if (!fa_shape_ok(S, H, KVH, D)) return hipErrorInvalidValue;
-  const float sl2 = scale * 1.4426950408889634f;
-  const size_t lds = 4 * TILE_BYTES;
-  // deferred-max threshold (log2 units; 0 = rescale on every new max): 8 takes the S=8192 causal
-  // forward from 0.700 to 0.660 ms, same fp32-reference error (tools/gpu_sessions/run_r2r.sh)
-  static const float thr = [] {
-    const char* v = getenv("DSTACK_AMD_FA_RESCALE_THR");
-    return v ? (float)atof(v) : 8.f;
-  }();
-  // 8 waves (one 256-row workgroup per CU) by default: 0.710 vs 0.720 ms at S=8192, three
-  // interleaved same-box runs (tools/gpu_sessions/run_r1s.sh); DSTACK_AMD_FA_FWD_WAVES=4 selects the 4-wave form
-  static const int waves = [] {
-    const char* v = getenv("DSTACK_AMD_FA_FWD_WAVES");
-    return (v && atoi(v) == 4) ? 4 : 8;
-  }();
-  static const bool pf = [] {
-    const char* v = getenv("DSTACK_AMD_FA_FWD_PF");
-    return !(v && atoi(v) == 0);
-  }();
-  static const int prio = [] {
-    const char* v = getenv("DSTACK_AMD_FA_PRIO");
-    return v ? atoi(v) : 0;
-  }();
-  static const bool stag = [] {
-    const char* v = getenv("DSTACK_AMD_FA_FWD_STAG");
-    return v && atoi(v) == 1;
-  }();
-  static const bool half_prio = [] {
-    const char* v = getenv("DSTACK_AMD_FA_HALF_PRIO");
-    return v && atoi(v) == 1;
-  }();
-  // K/V through buffer descriptors (DSTACK_AMD_FA_FWD_BUF=0 selects global_load_lds): forward
-  // 0.647-0.663 vs 0.660-0.679 ms, S=8192, 3 interleaved runs (profiles/fa_dq_fwd_ab_r8w.txt)
-  static const bool fwd_buf_env = [] {
-    const char* v = getenv("DSTACK_AMD_FA_FWD_BUF");
-    return !(v && atoi(v) == 0);
-  }();
-  const bool fwd_buf = fwd_buf_env && (long)S * (H + 2 * KVH) * HD * 2 < (1L << 31);
-  static const int fwd_pfd = [] {  // S-phase K reads in flight (buffer-DMA form): 4 or 8 (A/B)
-    const char* v = getenv("DSTACK_AMD_FA_FWD_PFD");
-    return (v && atoi(v) == 8) ? 8 : 4;
-  }();
-  if (waves == 8 && S % 256 == 0) {
-    const int grid = B * H * (S / 256);
-    if (causal && pf && half_prio)
-      fa_fwd_kernel<true, 8, true, 3><<<grid, 512, lds, st>>>((const bf16_t*)qkv, (bf16_t*)out, lse, B, S, H, KVH, sl2,
-                                                            thr);
-    else if (causal && pf && stag)
-      fa_fwd_kernel<true, 8, true, 0, true><<<grid, 512, 6 * TILE_BYTES, st>>>((const bf16_t*)qkv, (bf16_t*)out, lse, B, S,
-                                                                            H, KVH, sl2, thr);
-    else if (causal && pf && prio == 1)
-      fa_fwd_kernel<true, 8, true, 1><<<grid, 512, lds, st>>>((const bf16_t*)qkv, (bf16_t*)out, lse, B, S, H, KVH, sl2,
-                                                            thr);
-    else if (causal && pf && prio == 2)
-      fa_fwd_kernel<true, 8, true, 2><<<grid, 512, lds, st>>>((const bf16_t*)qkv, (bf16_t*)out, lse, B, S, H, KVH, sl2,
-                                                            thr);
-    else if (causal && pf && fwd_buf && fwd_pfd == 8)
-      fa_fwd_kernel<true, 8, true, 0, false, true, 8><<<grid, 512, lds, st>>>((const bf16_t*)qkv, (bf16_t*)out, lse, B,
-                                                                            S, H, KVH, sl2, thr);
-    else if (causal && pf && fwd_buf)
-      fa_fwd_kernel<true, 8, true, 0, false, true><<<grid, 512, lds, st>>>((const bf16_t*)qkv, (bf16_t*)out, lse, B, S,
-                                                                         H, KVH, sl2, thr);
-    else if (causal && pf)
-      fa_fwd_kernel<true, 8><<<grid, 512, lds, st>>>((const bf16_t*)qkv, (bf16_t*)out, lse, B, S, H, KVH, sl2, thr);
-    else if (causal)
-      fa_fwd_kernel<true, 8, false><<<grid, 512, lds, st>>>((const bf16_t*)qkv, (bf16_t*)out, lse, B, S, H, KVH, sl2, thr);
-    else
-      fa_fwd_kernel<false, 8><<<grid, 512, lds, st>>>((const bf16_t*)qkv, (bf16_t*)out, lse, B, S, H, KVH, sl2, thr);
-    return hipGetLastError();
-  }
-  const int grid = B * H * (S / 128);
-  if (causal)
-    fa_fwd_kernel<true><<<grid, 256, lds, st>>>((const bf16_t*)qkv, (bf16_t*)out, lse, B, S, H, KVH, sl2, thr);
-  else
-    fa_fwd_kernel<false><<<grid, 256, lds, st>>>((const bf16_t*)qkv, (bf16_t*)out, lse, B, S, H, KVH, sl2, thr);
+  const FaFwdPlan p = fa_fwd_plan(B, S, H, KVH, causal != 0);
+  const FaFwdKernel k = causal ? fa_fwd_select<true>(p.form) : fa_fwd_select<false>(p.form);
+  if (k == nullptr) return hipErrorInvalidValue;
+  k<<<p.grid, p.block, p.lds, st>>>((const bf16_t*)qkv, (bf16_t*)out, lse, B, S, H, KVH,
+                                    scale * 1.4426950408889634f, fa_sw().rescale_thr);
   return hipGetLastError();
 }
 
-// dS spill for the recompute-free dQ pass (DSTACK_AMD_FA_DQ=ds|recompute): B*H*S*S bf16 of
-// workspace, used while it stays under DSTACK_AMD_FA_DS_MAX_GB (default 16)
-static bool fa_ds_spill(int B, int S, int H) {
-  static const int mode = [] {
-    const char* v = getenv("DSTACK_AMD_FA_DQ");
-    return (v && std::string(v) == "ds") ? 1 : 0;
-  }();
-  static const double max_gb = [] {
-    const char* v = getenv("DSTACK_AMD_FA_DS_MAX_GB");
-    return v ? atof(v) : 16.0;
-  }();
-  return mode == 1 && (double)B * H * S * S * 2 <= max_gb * 1e9;
+// ---- backward -----------------------------------------------------------------------------------
+enum class FaDkdv { W4, W8, DEC, DEC_EARLY };  // 4 waves, 8 waves, 8 waves with decoupled halves
+struct FaBwdPlan {
+  // dK/dV pass; the flags and pf select the instantiation of the 8-wave kernel (W8)
+  FaDkdv dkdv;
+  bool hp, spill, gqa, p16;
+  int pf;
+  int dkdv_grid, dkdv_block;
+  size_t dkdv_lds;
+  // dQ pass: the recompute kernel, or with `spill` one GEMM over the spilled dS (dq_hp, dq_pf unused)
+  int dq_waves, dq_pf;
+  bool dq_hp;
+  int dq_grid, dq_block;
+  size_t dq_lds;
+  bool rope_fused;  // the RoPE backward runs in the dQ epilogue and the dK/dV reduction
+};
+// dK/dV precedence, first match wins (an 8-wave-only switch further down is then ignored):
+//   DSTACK_AMD_FA_DQ=ds within DS_MAX_GB   8 waves writing dS, fp32 partials, PF 0 (overrides 4w too)
+//   DSTACK_AMD_FA_DKDV=4w                  4 waves
+//   DSTACK_AMD_FA_HALF_PRIO=1              8 waves, priority for waves 4-7, PF 2 when DKDV_PF is 2, else PF 0
+//   DSTACK_AMD_FA_DKDV_GQA=1               8 waves, summed over the GQA group in the workgroup, PF 0
+//   DSTACK_AMD_FA_DKDV_DEC=1|2             decoupled halves (2: early operand reads); needs DKDV_PF=2
+//   DSTACK_AMD_FA_DKDV_PF=1                8 waves, PF 1
+//   default (PF 2, DSTACK_AMD_FA_DKDV_BF16 unset or 1)   8 waves, PF 2, bf16 partials
+//   DSTACK_AMD_FA_DKDV_BF16=0              8 waves, PF 2, fp32 partials
+//   DSTACK_AMD_FA_DKDV_PF=0                8 waves, PF 0
+// DKDV_PF counts as 0 when qkv is 2^31 bytes or more.
+// dQ precedence: the dS GEMM with the spill (8 waves when S % 256 == 0); else 4 waves with
+// DSTACK_AMD_FA_DQ_WAVES=4 or S % 256 != 0; else 8 waves, and for the causal pass HALF_PRIO (PF 0),
+// then DSTACK_AMD_FA_DQ_PF (0 when qkv is 2^31 bytes or more).
+static FaBwdPlan fa_bwd_plan(int B, int S, int H, int KVH, bool causal, bool has_rope) {
+  const FaSwitches& sw = fa_sw();
+  const bool small = fa_qkv_under_2g(S, H, KVH);
+  const int pf = small ? sw.dkdv_pf : 0;
+  FaBwdPlan p = {};
+  p.dkdv = FaDkdv::W8;
+  p.spill = sw.dq_ds && (double)B * H * S * S * 2 <= sw.ds_max_gb * 1e9;
+  if (p.spill) {
+  } else if (sw.dkdv_4w) {
+    p.dkdv = FaDkdv::W4;
+  } else if (sw.half_prio) {
+    p.hp = true;
+    p.pf = pf == 2 ? 2 : 0;
+  } else if (sw.dkdv_gqa) {
+    p.gqa = true;
+  } else if (sw.dkdv_dec >= 1 && pf == 2) {
+    p.dkdv = sw.dkdv_dec == 2 ? FaDkdv::DEC_EARLY : FaDkdv::DEC;
+  } else {
+    p.pf = pf;
+    p.p16 = sw.dkdv_bf16 && pf == 2;
+  }
+  p.dkdv_grid = (p.gqa ? B * KVH : B * H) * (S / 128);
+  p.dkdv_block = p.dkdv == FaDkdv::W4 ? 256 : 512;
+  p.dkdv_lds = p.dkdv == FaDkdv::W4 ? 2 * (2 * 64 * 256 + 8 * 64) : (p.dkdv == FaDkdv::W8 ? FA_LDS_DKDV8 : FA_LDS_DKDV8D);
+  p.dq_waves = ((p.spill || sw.dq_waves == 8) && S % 256 == 0) ? 8 : 4;
+  if (!p.spill && causal && p.dq_waves == 8) {
+    p.dq_hp = sw.half_prio;
+    p.dq_pf = (sw.half_prio || !small) ? 0 : sw.dq_pf;
+  }
+  p.dq_grid = B * H * (S / (32 * p.dq_waves));
+  p.dq_block = 64 * p.dq_waves;
+  p.dq_lds = (p.spill && p.dq_waves == 8 ? 6 : 4) * TILE_BYTES;  // the dS GEMM stages K + NW/4 dS^T tiles
+  p.rope_fused = has_rope && !p.gqa && !p.spill;
+  return p;
+}
+
+using FaDkdv8Kernel = void (*)(const bf16_t*, const bf16_t*, const float*, const float*, float*, float*, int, int,
+                               int, int, float, bf16_t*, bf16_t*);
+using FaDkdv8dKernel = void (*)(const bf16_t*, const bf16_t*, const float*, const float*, float*, float*, int, int,
+                                int, int, float, int, unsigned long long*);
+using FaDqKernel = void (*)(const bf16_t*, const bf16_t*, const float*, const float*, bf16_t*, int, int, int, int,
+                            float, const float*, const float*);
+using FaDqDsKernel = void (*)(const bf16_t*, const bf16_t*, bf16_t*, int, int, int, int, float);
+
+// The selectors list every (flags) tuple a plan can hold beside its instantiation, whose template
+// arguments repeat the tuple; anything else is nullptr, which the launcher reports.
+template <bool C>
+static FaDkdv8Kernel fa_dkdv8_select(const FaBwdPlan& p) {
+  auto is = [&](bool hp, bool spill, bool gqa, int pf, bool p16) {
+    return p.hp == hp && p.spill == spill && p.gqa == gqa && p.pf == pf && p.p16 == p16;
+  };  //                      HP   SPILL   GQA  PF  P16                      <C,    HP,   SPILL,   GQA,    TR, PF,  P16>
+  if (is(false, false, false, 2, true)) return fa_bwd_dkdv8_kernel<C, false, false, false, false, 2, true>;
+  if (is(false, false, false, 2, false)) return fa_bwd_dkdv8_kernel<C, false, false, false, false, 2>;
+  if (is(false, false, false, 1, false)) return fa_bwd_dkdv8_kernel<C, false, false, false, false, 1>;
+  if (is(false, false, false, 0, false)) return fa_bwd_dkdv8_kernel<C>;
+  if (is(true, false, false, 2, false)) return fa_bwd_dkdv8_kernel<C, true, false, false, false, 2>;
+  if (is(true, false, false, 0, false)) return fa_bwd_dkdv8_kernel<C, true>;
+  if (is(false, true, false, 0, false)) return fa_bwd_dkdv8_kernel<C, false, true>;
+  if (is(false, false, true, 0, false)) return fa_bwd_dkdv8_kernel<C, false, false, true>;
+  return nullptr;
+}
+template <bool C>
+static FaDkdv8dKernel fa_dkdv8d_select(FaDkdv form) {
+  return form == FaDkdv::DEC_EARLY ? fa_bwd_dkdv8d_kernel<C, false, true> : fa_bwd_dkdv8d_kernel<C>;
+}
+template <bool C>
+static FaDqKernel fa_dq_select(const FaBwdPlan& p) {
+  auto is = [&](int waves, bool hp, int pf) { return p.dq_waves == waves && p.dq_hp == hp && p.dq_pf == pf; };
+  if (is(4, false, 0)) return fa_bwd_dq_kernel<C>;
+  if (is(8, false, 0)) return fa_bwd_dq_kernel<C, 8>;
+  if constexpr (C) {  // fa_bwd_plan gives the non-causal pass neither the priority nor the read pipeline
+    if (is(8, false, 1)) return fa_bwd_dq_kernel<true, 8, false, 1>;
+    if (is(8, false, 2)) return fa_bwd_dq_kernel<true, 8, false, 2>;
+    if (is(8, true, 0)) return fa_bwd_dq_kernel<true, 8, true>;
+  }
+  return nullptr;
+}
+template <bool C>
+static FaDqDsKernel fa_dq_ds_select(int waves) {
+  return waves == 8 ? fa_bwd_dq_ds_kernel<C, 8> : fa_bwd_dq_ds_kernel<C, 4>;
 }
 
 // workspace: delta (B*H*S fp32) + dkp + dvp (2 * B*S*H*128 fp32) [+ dS spill (B*H*S*S bf16)]
 extern "C" size_t dsa_fa_bwd_workspace(int B, int S, int H) {
-  return (size_t)B * H * S * 4 + 2 * (size_t)B * S * H * HD * 4 +
-         (fa_ds_spill(B, S, H) ? (size_t)B * H * S * S * 2 : 0);
+  const bool spill = fa_bwd_plan(B, S, H, H, true, false).spill;  // a function of B, S and H only
+  return (size_t)B * H * S * 4 + 2 * (size_t)B * S * H * HD * 4 + (spill ? (size_t)B * H * S * S * 2 : 0);
 }
 
 extern "C" hipError_t dsa_rope_qkv(const void* in, void* out, const float* cosT, const float* sinT, int rows, int S,
@@ -1678,282 +1651,70 @@ extern "C" hipError_t dsa_rope_qkv(const void* in, void* out, const float* cosT,
 // rcos / rsin (nullable, [S][64] fp32): q and k were rotated by RoPE after the projection (the qkv
 // GEMM's epilogue); dqkv is then the gradient w.r.t. the unrotated projection -- fused into the dQ
 // epilogue and the dK reduction on the default path, an in-place pass on the others.
-// The dQ pass on a second stream of the same device (DSTACK_AMD_FA_DQ_STREAM=1): it depends only on
-// the delta pass, like the dK/dV pass, so the two can share the CUs -- the workgroups of one fill
-// what the other's causal tail leaves idle.  The side stream is non-blocking (no implicit sync with
-// the legacy default stream); the caller's stream waits for it before anything reads dqkv.
-namespace {
-struct FaSide {
-  hipStream_t s = nullptr;
-  hipEvent_t ready = nullptr, done = nullptr;
-};
-FaSide* fa_side() {
-  static std::mutex mu;
-  static FaSide sides[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  std::lock_guard<std::mutex> g(mu);
-  FaSide& f = sides[dev];
-  if (f.s == nullptr) {
-    if (hipStreamCreateWithFlags(&f.s, hipStreamNonBlocking) != hipSuccess) return nullptr;
-    if (hipEventCreateWithFlags(&f.ready, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&f.done, hipEventDisableTiming) != hipSuccess)
-      return nullptr;
-  }
-  return &f;
-}
-}  // namespace
-
-extern "C" hipError_t dsa_fa_bwd(const void* qkv, const void* out, const void* dout, const float* lse,
-                                 void* dqkv, void* workspace, int B, int S, int H, int KVH, int D,
+extern "C" hipError_t dsa_fa_bwd(const void* qkv_, const void* out, const void* dout_, const float* lse,
+                                 void* dqkv_, void* workspace, int B, int S, int H, int KVH, int D,
                                  float scale, int causal, const float* rcos, const float* rsin,
                                  hipStream_t st) {
   if (!fa_shape_ok(S, H, KVH, D)) return hipErrorInvalidValue;
+  const FaBwdPlan p = fa_bwd_plan(B, S, H, KVH, causal != 0, rcos != nullptr);
+  const bf16_t* qkv = (const bf16_t*)qkv_;
+  const bf16_t* dout = (const bf16_t*)dout_;
+  bf16_t* dqkv = (bf16_t*)dqkv_;
   const float sl2 = scale * 1.4426950408889634f;
   float* delta = (float*)workspace;
   float* dkp = delta + (size_t)B * H * S;
   float* dvp = dkp + (size_t)B * S * H * HD;
+  bf16_t* dsg = p.spill ? (bf16_t*)(dvp + (size_t)B * S * H * HD) : nullptr;
   const long rows = (long)B * S * H;
   if (H % 8 == 0 && S % 32 == 0)
-    fa_bwd_delta_tiled_kernel<<<B * (S / 32) * (H / 8), 256, 0, st>>>(
-        (const bf16_t*)out, (const bf16_t*)dout, delta, B, S, H);
+    fa_bwd_delta_tiled_kernel<<<B * (S / 32) * (H / 8), 256, 0, st>>>((const bf16_t*)out, dout, delta, B, S, H);
   else
-    fa_bwd_delta_kernel<<<(int)((rows + 15) / 16), 256, 0, st>>>((const bf16_t*)out,
-                                                                 (const bf16_t*)dout, delta, B, S, H);
+    fa_bwd_delta_kernel<<<(int)((rows + 15) / 16), 256, 0, st>>>((const bf16_t*)out, dout, delta, B, S, H);
   DSA_CHECK(hipGetLastError());
-  const int grid = B * H * (S / 128);
-  // dK/dV q-tile per pipeline stage: 64 rows (default) or 128 (DSTACK_AMD_FA_DKDV_QT=128: half
-  // the barriers, 130 KiB of LDS)
-  static const int dkdv_qt = [] {
-    const char* v = getenv("DSTACK_AMD_FA_DKDV_QT");
-    return (v && atoi(v) == 128) ? 128 : 64;
-  }();
-  const size_t lds_kv = 2 * (2 * (size_t)dkdv_qt * 256 + 8 * (size_t)dkdv_qt);
-  const size_t lds_q = 4 * TILE_BYTES;
-  // dK/dV kernel: the 8-wave K/V-resident variant is the default (2.10 vs 2.53 ms for the whole
-  // backward at S=8192, same box); DSTACK_AMD_FA_DKDV=4w selects the 4-wave register-resident one.
-  // Opt-in variants measured slower and kept for A/B only (profiles/fa_dkdv_seed_ab_r4h.txt, 3
-  // interleaved runs, whole backward S=8192): default 675-684 TFLOP/s, 'seed' (row-constant seeded
-  // dK/dV accumulators) 583-592, '64kv' (64 keys per wave, V in registers) 576-581.
-  static const int dkdv_kind = [] {  // 8 = 8-wave (default), 4 = 4-wave, 64 / 65 = 64 keys per wave
-    const char* v = getenv("DSTACK_AMD_FA_DKDV");
-    if (!v) return 8;
-    const std::string s(v);
-    return s == "4w" ? 4 : (s == "64k" ? 64 : (s == "64kv" ? 65 : (s == "seed" ? 9 : 8)));
-  }();
-  const bool dkdv8 = dkdv_kind == 8 || dkdv_kind == 9;
-  // dQ pass: 8 waves / 256 query rows per workgroup when S % 256 == 0 (DSTACK_AMD_FA_DQ_WAVES=4|8).
-  // Whole backward at S=8192, same box, 3 interleaved runs each (tools/gpu_sessions/run_r1t.sh): 4 waves 2.06-2.08
-  // ms; 8 waves 2.04-2.07; 8 waves with the dP accumulator seeded with -delta ('row constant')
-  // 2.00-2.05 -- the seeding is kept for 8 waves only: with 4 waves it measured 2.14-2.17 ms.
-  static const int dq_waves_env = [] {
-    const char* v = getenv("DSTACK_AMD_FA_DQ_WAVES");
-    return (v && atoi(v) == 4) ? 4 : 8;
-  }();
-  const int dq_waves = (dq_waves_env == 8 && S % 256 == 0) ? 8 : 4;
-  static const bool half_prio = [] {  // static priority for waves 4-7 (see the forward's PRIO 3)
-    const char* v = getenv("DSTACK_AMD_FA_HALF_PRIO");
-    return v && atoi(v) == 1;
-  }();
-  // GQA-summed dK/dV (one workgroup per KV head and key block, bf16 written directly, no reduce
-  // kernel): DSTACK_AMD_FA_DKDV_GQA=1
-  static const bool dkdv_gqa_env = [] {
-    const char* v = getenv("DSTACK_AMD_FA_DKDV_GQA");
-    return v && atoi(v) == 1;
-  }();
-  const bool dkdv_gqa = dkdv_gqa_env && dkdv_kind == 8 && !half_prio && !fa_ds_spill(B, S, H);
-  const bool rope_fused = rcos != nullptr && !dkdv_gqa && !fa_ds_spill(B, S, H);
-  const float* rq = rope_fused ? rcos : nullptr;
-  const float* rsq = rope_fused ? rsin : nullptr;
-  auto rope_after = [&]() -> hipError_t {  // the paths without the fused RoPE backward
-    if (rcos == nullptr || rope_fused) return hipSuccess;
-    return dsa_rope_qkv(dqkv, dqkv, rcos, rsin, B * S, S, H + 2 * KVH, H + KVH, HD, 1, st);
-  };
-  // S/dP read pipeline of the 8-wave dK/dV pass (DSTACK_AMD_FA_DKDV_PF=0|1|2, default 2).  Whole
-  // backward at S=8192, 3 interleaved runs (profiles/fa_bwd_pf_ab_r8t.txt): PF 0 2.031-2.045 ms,
-  // PF 2 1.959-1.963 ms.  The dQ pass's counterpart (DSTACK_AMD_FA_DQ_PF=1|2) measured no gain.
-  static const int dkdv_pf_env = [] {
-    const char* v = getenv("DSTACK_AMD_FA_DKDV_PF");
-    return v ? atoi(v) : 2;
-  }();
-  // the PF form addresses a Q / dO tile through a buffer descriptor with 32-bit offsets
-  const int dkdv_pf = ((long)S * (H + 2 * KVH) * HD * 2 < (1L << 31)) ? dkdv_pf_env : 0;
-  // dQ pass: DSTACK_AMD_FA_DQ_PF=0|1|2, default 1 (whole backward 1.924-1.946 vs 1.945-1.964 ms;
-  // 2 spills and measured 1.976-2.000, profiles/fa_dq_fwd_ab_r8w.txt)
-  static const int dq_pf_env = [] {
-    const char* v = getenv("DSTACK_AMD_FA_DQ_PF");
-    return v ? atoi(v) : 1;
-  }();
-  const int dq_pf = ((long)S * (H + 2 * KVH) * HD * 2 < (1L << 31)) ? dq_pf_env : 0;
-  // decoupled halves (fa_bwd_dkdv8d_kernel): DSTACK_AMD_FA_DKDV_DEC=1, waves 4-7 started
-  // DSTACK_AMD_FA_DKDV_STAG x 64 clocks late
-  static const int dkdv_dec_env = [] {
-    const char* v = getenv("DSTACK_AMD_FA_DKDV_DEC");
-    return v ? atoi(v) : 0;
-  }();
-  static const int dkdv_stag = [] {
-    const char* v = getenv("DSTACK_AMD_FA_DKDV_STAG");
-    return v ? atoi(v) : 0;
-  }();
-  const bool dkdv_dec = dkdv_dec_env >= 1 && dkdv_kind == 8 && !half_prio && !dkdv_gqa && dkdv_pf >= 2;
-  // bf16 per-query-head dK/dV partials (DSTACK_AMD_FA_DKDV_BF16=1|0): the default 8-wave PF-2 pass only
-  static const bool dkdv_bf16_env = [] {
-    const char* v = getenv("DSTACK_AMD_FA_DKDV_BF16");
-    return v ? atoi(v) == 1 : true;
-  }();
-  const bool p16 = dkdv_bf16_env && dkdv_kind == 8 && dkdv_pf == 2 && !dkdv_dec && !half_prio && !dkdv_gqa &&
-                   !fa_ds_spill(B, S, H);
-  const size_t lds_dec = 2 * 128 * 256 + 4 * (2 * 32 * 256 + 512) + 16;
-#define DSA_DKDV(C, N)                                                                                 \
-  do {                                                                                                 \
-    if (dkdv_dec && dkdv_dec_env == 2) {                                                               \
-      fa_bwd_dkdv8d_kernel<C, false, true><<<grid, 512, lds_dec, st>>>(                                  \
-          (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2, dkdv_stag, nullptr); \
-    } else if (dkdv_dec) {                                                                             \
-      fa_bwd_dkdv8d_kernel<C><<<grid, 512, lds_dec, st>>>((const bf16_t*)qkv, (const bf16_t*)dout, lse,  \
-                                                          delta, dkp, dvp, B, S, H, KVH, sl2, dkdv_stag,  \
-                                                          nullptr);                                      \
-    } else if (dkdv_kind >= 64 && S % 256 == 0) {                                                      \
-      if (dkdv_kind == 64)                                                                             \
-        fa_bwd_dkdv64_kernel<C, true><<<B * H * (S / 256), 256, 2 * (2 * TILE_BYTES + 512), st>>>(     \
-            (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2);         \
-      else                                                                                             \
-        fa_bwd_dkdv64_kernel<C, false><<<B * H * (S / 256), 256, 4 * TILE_BYTES + 2 * (2 * TILE_BYTES + 512), \
-                                         st>>>((const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, \
-                                               B, S, H, KVH, sl2);                                     \
-    } else if (dkdv_kind == 9) {                                                                      \
-      fa_bwd_dkdv8_kernel<C, true><<<grid, 512, 2 * 128 * 256 + 2 * (2 * TILE_BYTES + 512), st>>>(     \
-          (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2, nullptr);  \
-    } else if ((dkdv8 || dkdv_kind >= 64) && half_prio && dkdv_pf >= 2) {                              \
-      fa_bwd_dkdv8_kernel<C, false, true, false, false, false, 2>                                      \
-          <<<grid, 512, 2 * 128 * 256 + 2 * (2 * TILE_BYTES + 512), st>>>(                             \
-              (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2, nullptr); \
-    } else if ((dkdv8 || dkdv_kind >= 64) && half_prio) {                                              \
-      fa_bwd_dkdv8_kernel<C, false, true><<<grid, 512, 2 * 128 * 256 + 2 * (2 * TILE_BYTES + 512), st>>>( \
-          (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2, nullptr);  \
-    } else if (dkdv_gqa) {                                                                             \
-      fa_bwd_dkdv8_kernel<C, false, false, false, true>                                                \
-          <<<B * KVH * (S / 128), 512, 2 * 128 * 256 + 2 * (2 * TILE_BYTES + 512), st>>>(              \
-              (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2, nullptr, \
-              (bf16_t*)dqkv);                                                                          \
-    } else if (dkdv_pf == 1 && dkdv_kind == 8) {                                                       \
-      fa_bwd_dkdv8_kernel<C, false, false, false, false, false, 1>                                     \
-          <<<grid, 512, 2 * 128 * 256 + 2 * (2 * TILE_BYTES + 512), st>>>(                             \
-              (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2, nullptr); \
-    } else if (dkdv_pf >= 3 && dkdv_kind == 8) {                                                       \
-      fa_bwd_dkdv8_kernel<C, false, false, false, false, false, 3>                                     \
-          <<<grid, 512, 2 * 128 * 256 + 2 * (2 * TILE_BYTES + 512), st>>>(                             \
-              (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2, nullptr); \
-    } else if (p16) {                                                                                  \
-      fa_bwd_dkdv8_kernel<C, false, false, false, false, false, 2, true>                               \
-          <<<grid, 512, 2 * 128 * 256 + 2 * (2 * TILE_BYTES + 512), st>>>(                             \
-              (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2, nullptr); \
-    } else if (dkdv_pf == 2 && dkdv_kind == 8) {                                                       \
-      fa_bwd_dkdv8_kernel<C, false, false, false, false, false, 2>                                     \
-          <<<grid, 512, 2 * 128 * 256 + 2 * (2 * TILE_BYTES + 512), st>>>(                             \
-              (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2, nullptr); \
-    } else if (dkdv8 || dkdv_kind >= 64) {                                                             \
-      fa_bwd_dkdv8_kernel<C><<<grid, 512, 2 * 128 * 256 + 2 * (2 * TILE_BYTES + 512), st>>>(          \
-          (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2, nullptr);  \
-    } else                                                                                             \
-      fa_bwd_dkdv_kernel<C, N><<<grid, 256, lds_kv, st>>>((const bf16_t*)qkv, (const bf16_t*)dout, lse, \
-                                                          delta, dkp, dvp, B, S, H, KVH, sl2);         \
-  } while (0)
-  static const bool dq_stream_env = [] {
-    const char* v = getenv("DSTACK_AMD_FA_DQ_STREAM");
-    return v && atoi(v) == 1;
-  }();
-  FaSide* side = nullptr;  // set when the causal dQ pass runs on the side stream
-  // the caller's stream waits for the side stream's dQ pass before anything after this call
-  auto join = [&]() -> hipError_t { return side ? hipStreamWaitEvent(st, side->done, 0) : hipSuccess; };
-  if (fa_ds_spill(B, S, H)) {  // dK/dV pass writes dS; dQ is one GEMM over the spilled dS
-    bf16_t* dsg = (bf16_t*)(dvp + (size_t)B * S * H * HD);
-    const size_t lds8 = 2 * 128 * 256 + 2 * (2 * TILE_BYTES + 512);
-    if (causal)
-      fa_bwd_dkdv8_kernel<true, false, false, true><<<grid, 512, lds8, st>>>(
-          (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2, dsg);
-    else
-      fa_bwd_dkdv8_kernel<false, false, false, true><<<grid, 512, lds8, st>>>(
-          (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2, dsg);
-    DSA_CHECK(hipGetLastError());
-    const size_t lds_ds8 = 2 * 3 * TILE_BYTES, lds_ds4 = 2 * 2 * TILE_BYTES;
-    if (S % 256 == 0) {
-      if (causal)
-        fa_bwd_dq_ds_kernel<true, 8><<<B * H * (S / 256), 512, lds_ds8, st>>>((const bf16_t*)qkv, dsg, (bf16_t*)dqkv,
-                                                                             B, S, H, KVH, sl2);
-      else
-        fa_bwd_dq_ds_kernel<false, 8><<<B * H * (S / 256), 512, lds_ds8, st>>>((const bf16_t*)qkv, dsg,
-                                                                              (bf16_t*)dqkv, B, S, H, KVH, sl2);
-    } else {
-      if (causal)
-        fa_bwd_dq_ds_kernel<true, 4><<<grid, 256, lds_ds4, st>>>((const bf16_t*)qkv, dsg, (bf16_t*)dqkv, B, S, H,
-                                                                KVH, sl2);
-      else
-        fa_bwd_dq_ds_kernel<false, 4><<<grid, 256, lds_ds4, st>>>((const bf16_t*)qkv, dsg, (bf16_t*)dqkv, B, S, H,
-                                                                 KVH, sl2);
-    }
-  } else if (causal) {
-    hipStream_t qs = st;  // the dQ pass's stream
-    if (dq_stream_env && (side = fa_side()) != nullptr) {
-      DSA_CHECK(hipEventRecord(side->ready, st));  // after the delta pass
-      DSA_CHECK(hipStreamWaitEvent(side->s, side->ready, 0));
-      qs = side->s;
-    }
-    if (dkdv_qt == 128) DSA_DKDV(true, 4); else DSA_DKDV(true, 2);
-    DSA_CHECK(hipGetLastError());
-    if (dq_waves == 8 && half_prio)
-      fa_bwd_dq_kernel<true, 8, true><<<B * H * (S / 256), 512, lds_q, qs>>>(
-          (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, B, S, H, KVH, sl2, rq, rsq);
-    else if (dq_waves == 8 && dq_pf == 1)
-      fa_bwd_dq_kernel<true, 8, false, 1><<<B * H * (S / 256), 512, lds_q, qs>>>(
-          (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, B, S, H, KVH, sl2, rq, rsq);
-    else if (dq_waves == 8 && dq_pf >= 2)
-      fa_bwd_dq_kernel<true, 8, false, 2><<<B * H * (S / 256), 512, lds_q, qs>>>(
-          (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, B, S, H, KVH, sl2, rq, rsq);
-    else if (dq_waves == 8)
-      fa_bwd_dq_kernel<true, 8><<<B * H * (S / 256), 512, lds_q, qs>>>(
-          (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, B, S, H, KVH, sl2, rq, rsq);
-    else
-      fa_bwd_dq_kernel<true><<<grid, 256, lds_q, qs>>>((const bf16_t*)qkv, (const bf16_t*)dout, lse, delta,
-                                                       (bf16_t*)dqkv, B, S, H, KVH, sl2, rq, rsq);
-    if (side != nullptr) DSA_CHECK(hipEventRecord(side->done, qs));
+
+  // dK/dV pass: one launch per kernel signature
+  if (p.dkdv == FaDkdv::W4) {
+    const auto k = causal ? fa_bwd_dkdv_kernel<true> : fa_bwd_dkdv_kernel<false>;
+    k<<<p.dkdv_grid, p.dkdv_block, p.dkdv_lds, st>>>(qkv, dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2);
+  } else if (p.dkdv == FaDkdv::W8) {
+    const FaDkdv8Kernel k = causal ? fa_dkdv8_select<true>(p) : fa_dkdv8_select<false>(p);
+    if (k == nullptr) return hipErrorInvalidValue;
+    k<<<p.dkdv_grid, p.dkdv_block, p.dkdv_lds, st>>>(qkv, dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2, dsg,
+                                                     p.gqa ? dqkv : nullptr);
   } else {
-    if (dkdv_qt == 128) DSA_DKDV(false, 4); else DSA_DKDV(false, 2);
-    DSA_CHECK(hipGetLastError());
-    if (dq_waves == 8)
-      fa_bwd_dq_kernel<false, 8><<<B * H * (S / 256), 512, lds_q, st>>>(
-          (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, (bf16_t*)dqkv, B, S, H, KVH, sl2, rq, rsq);
-    else
-      fa_bwd_dq_kernel<false><<<grid, 256, lds_q, st>>>((const bf16_t*)qkv, (const bf16_t*)dout, lse,
-                                                        delta, (bf16_t*)dqkv, B, S, H, KVH, sl2, rq, rsq);
+    const FaDkdv8dKernel k = causal ? fa_dkdv8d_select<true>(p.dkdv) : fa_dkdv8d_select<false>(p.dkdv);
+    k<<<p.dkdv_grid, p.dkdv_block, p.dkdv_lds, st>>>(qkv, dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2,
+                                                     fa_sw().dkdv_stag, nullptr);
   }
-#undef DSA_DKDV
   DSA_CHECK(hipGetLastError());
-  if (dkdv_gqa) {  // dK/dV already summed over the group, in dqkv
-    DSA_CHECK(join());
-    return rope_after();
+
+  // dQ pass: one GEMM over the spilled dS, or the recompute kernel
+  if (p.spill) {
+    const FaDqDsKernel k = causal ? fa_dq_ds_select<true>(p.dq_waves) : fa_dq_ds_select<false>(p.dq_waves);
+    k<<<p.dq_grid, p.dq_block, p.dq_lds, st>>>(qkv, dsg, dqkv, B, S, H, KVH, sl2);
+  } else {
+    const FaDqKernel k = causal ? fa_dq_select<true>(p) : fa_dq_select<false>(p);
+    if (k == nullptr) return hipErrorInvalidValue;
+    k<<<p.dq_grid, p.dq_block, p.dq_lds, st>>>(qkv, dout, lse, delta, dqkv, B, S, H, KVH, sl2,
+                                               p.rope_fused ? rcos : nullptr, p.rope_fused ? rsin : nullptr);
   }
-  if (rope_fused) {
-    const long work = (long)B * S * KVH * (HD / 16);
-    int g = (int)((work + 255) / 256);
-    if (g > 4096) g = 4096;
-    if (p16)
-      fa_bwd_reduce_kv_rope_kernel<true><<<g, 256, 0, st>>>(dkp, dvp, (bf16_t*)dqkv, B, S, H, KVH, rcos, rsin);
-    else
-      fa_bwd_reduce_kv_rope_kernel<false><<<g, 256, 0, st>>>(dkp, dvp, (bf16_t*)dqkv, B, S, H, KVH, rcos, rsin);
-    DSA_CHECK(hipGetLastError());
-    return join();
-  }
-  const long work = (long)B * S * KVH * (HD / 8);
-  int g = (int)((work + 255) / 256);
-  if (g > 4096) g = 4096;
-  if (p16)
-    fa_bwd_reduce_kv_kernel<true><<<g, 256, 0, st>>>(dkp, dvp, (bf16_t*)dqkv, B, S, H, KVH);
-  else
-    fa_bwd_reduce_kv_kernel<false><<<g, 256, 0, st>>>(dkp, dvp, (bf16_t*)dqkv, B, S, H, KVH);
   DSA_CHECK(hipGetLastError());
-  DSA_CHECK(join());
-  return rope_after();
+
+  // dK/dV of the GQA group: already summed (gqa), or the reduction over the per-query-head partials
+  if (!p.gqa) {
+    const long work = (long)B * S * KVH * (HD / (p.rope_fused ? 16 : 8));
+    const int g = (int)std::min<long>((work + 255) / 256, 4096);
+    if (p.rope_fused) {
+      const auto k = p.p16 ? fa_bwd_reduce_kv_rope_kernel<true> : fa_bwd_reduce_kv_rope_kernel<false>;
+      k<<<g, 256, 0, st>>>(dkp, dvp, dqkv, B, S, H, KVH, rcos, rsin);
+    } else {
+      const auto k = p.p16 ? fa_bwd_reduce_kv_kernel<true> : fa_bwd_reduce_kv_kernel<false>;
+      k<<<g, 256, 0, st>>>(dkp, dvp, dqkv, B, S, H, KVH);
+    }
+    DSA_CHECK(hipGetLastError());
+  }
+  if (rcos == nullptr || p.rope_fused) return hipSuccess;
+  return dsa_rope_qkv(dqkv, dqkv, rcos, rsin, B * S, S, H + 2 * KVH, H + KVH, HD, 1, st);  // not fused above
 }
 
 // Diagnostic: one causal dK/dV pass (8-wave kernel) with waves 0 and 4 of workgroup 0 stamping 5
@@ -1962,20 +1723,15 @@ extern "C" hipError_t dsa_fa_dkdv_trace(const void* qkv, const void* dout, const
                                         float* dkp, float* dvp, unsigned long long* trace, int B, int S, int H,
                                         int KVH, float sl2, hipStream_t st) {
   if (S % 128) return hipErrorInvalidValue;
-  const char* dec = getenv("DSTACK_AMD_FA_DKDV_DEC");
-  if (dec && atoi(dec) >= 1) {  // the decoupled-halves form: stamp 4 is after the half's rendezvous
-    const char* sg = getenv("DSTACK_AMD_FA_DKDV_STAG");
-    const size_t lds_dec = 2 * 128 * 256 + 4 * (2 * 32 * 256 + 512) + 16;
-    if (atoi(dec) == 2)
-      fa_bwd_dkdv8d_kernel<true, true, true><<<B * H * (S / 128), 512, lds_dec, st>>>(
-          (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2, sg ? atoi(sg) : 0, trace);
-    else
-      fa_bwd_dkdv8d_kernel<true, true><<<B * H * (S / 128), 512, lds_dec, st>>>(
-          (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2, sg ? atoi(sg) : 0, trace);
+  const FaSwitches& sw = fa_sw();
+  const int grid = B * H * (S / 128);
+  if (sw.dkdv_dec >= 1) {  // the decoupled-halves form: stamp 4 is after the half's rendezvous
+    const FaDkdv8dKernel k = sw.dkdv_dec == 2 ? fa_bwd_dkdv8d_kernel<true, true, true> : fa_bwd_dkdv8d_kernel<true, true>;
+    k<<<grid, 512, FA_LDS_DKDV8D, st>>>((const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH,
+                                        sl2, sw.dkdv_stag, trace);
     return hipGetLastError();
   }
-  const size_t lds8 = 2 * 128 * 256 + 2 * (2 * TILE_BYTES + 512);
-  fa_bwd_dkdv8_kernel<true, false, false, false, false, true, 2><<<B * H * (S / 128), 512, lds8, st>>>(
-      (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2, (bf16_t*)trace);
+  fa_bwd_dkdv8_kernel<true, false, false, false, true, 2><<<grid, 512, FA_LDS_DKDV8, st>>>(
+      (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, dkp, dvp, B, S, H, KVH, sl2, (bf16_t*)trace, nullptr);
   return hipGetLastError();
 }

@@ -292,8 +292,10 @@ def test_flash_attention_kernel_variants_agree(gpu, tmp_path):
     dQ pass's (DSTACK_AMD_FA_DQ_PF=1|2, causal), and the dK/dV pass with decoupled halves
     (DSTACK_AMD_FA_DKDV_DEC=1, with and without a stagger; bit-identical to the barrier form with fp32
     partials), and the default pass with fp32 instead of bf16 per-query-head dK/dV partials
-    (DSTACK_AMD_FA_DKDV_BF16=0).  The switches are read once per process, so each variant runs in a
-    child process."""
+    (DSTACK_AMD_FA_DKDV_BF16=0), and the forms that tensors of 2 GiB and more fall back to: the forward
+    without buffer descriptors (DSTACK_AMD_FA_FWD_BUF=0) and the dQ pass without its read pipeline
+    (DSTACK_AMD_FA_DQ_PF=0).  The switches are read once per process, so each variant runs in a
+    child process, whose environment carries no DSTACK_AMD_FA_* variable but the variant's own."""
     import os
     import subprocess
     import sys
@@ -329,15 +331,11 @@ def test_flash_attention_kernel_variants_agree(gpu, tmp_path):
                 "dkdv_dec_nc": {"DSTACK_AMD_FA_DKDV_DEC": "1"}, "dkdv_dec_1152": {"DSTACK_AMD_FA_DKDV_DEC": "1"},
                 "dkdv_dec_early": {"DSTACK_AMD_FA_DKDV_DEC": "2"},
                 "p32": {"DSTACK_AMD_FA_DKDV_BF16": "0"}, "p32_1152": {"DSTACK_AMD_FA_DKDV_BF16": "0"},
-                "p32_nc": {"DSTACK_AMD_FA_DKDV_BF16": "0"}, "p32_1152_nc": {"DSTACK_AMD_FA_DKDV_BF16": "0"}}
+                "p32_nc": {"DSTACK_AMD_FA_DKDV_BF16": "0"}, "p32_1152_nc": {"DSTACK_AMD_FA_DKDV_BF16": "0"},
+                "fwd_buf0": {"DSTACK_AMD_FA_FWD_BUF": "0"}, "dq_pf0": {"DSTACK_AMD_FA_DQ_PF": "0"}}
     out = {}
     for name, extra in variants.items():
-        env = dict(os.environ)
-        for k in ("DSTACK_AMD_FA_DKDV", "DSTACK_AMD_FA_FWD_WAVES", "DSTACK_AMD_FA_DQ_WAVES", "DSTACK_AMD_FA_FWD_PF",
-                  "DSTACK_AMD_FA_RESCALE_THR", "DSTACK_AMD_FA_FWD_STAG", "DSTACK_AMD_FA_HALF_PRIO", "DSTACK_AMD_FA_DQ",
-                  "DSTACK_AMD_FA_DKDV_GQA", "DSTACK_AMD_FA_DKDV_PF", "DSTACK_AMD_FA_DQ_PF", "DSTACK_AMD_FA_DKDV_DEC",
-                  "DSTACK_AMD_FA_DKDV_STAG", "DSTACK_AMD_FA_DKDV_BF16"):
-            env.pop(k, None)
+        env = {k: v for k, v in os.environ.items() if not k.startswith("DSTACK_AMD_FA_")}
         env.update(extra)
         sn, causal = shape.get(name, (S, True))
         subprocess.run([sys.executable, "-c", script, str(tmp_path / f"{name}.pt"), str(sn), "1" if causal else "0"],
@@ -348,8 +346,9 @@ def test_flash_attention_kernel_variants_agree(gpu, tmp_path):
     # with the default; the other dK/dV forms keep fp32 partials and are compared with the default pass
     # in that form
     for name in ("dkdv4", "fwd4_dq4", "fwd_pf0", "exact_max", "fwd_stag", "half_prio", "dq_ds", "dkdv_gqa",
-                 "dkdv_pf0", "dkdv_pf1", "dq_pf1", "dq_pf2", "dkdv_dec", "dkdv_dec_stag"):
-        ref = "default" if name in ("fwd4_dq4", "fwd_pf0", "exact_max", "fwd_stag", "dq_pf1", "dq_pf2") else "p32"
+                 "dkdv_pf0", "dkdv_pf1", "dq_pf1", "dq_pf2", "dkdv_dec", "dkdv_dec_stag", "fwd_buf0", "dq_pf0"):
+        ref = "default" if name in ("fwd4_dq4", "fwd_pf0", "exact_max", "fwd_stag", "dq_pf1", "dq_pf2", "fwd_buf0",
+                                    "dq_pf0") else "p32"
         ref_o, ref_g = out[ref]["o"].float(), out[ref]["g"].float()
         o, g = out[name]["o"].float(), out[name]["g"].float()
         assert ((o - ref_o).norm() / ref_o.norm()).item() < 2e-3, name
