@@ -48,6 +48,9 @@ def main():
     ap.add_argument("--top-p", type=float, default=1.0, help="nucleus sampling (1 = off)")
     ap.add_argument("--top-k", type=int, default=0, help="top-k sampling (0 = off)")
     ap.add_argument("--min-p", type=float, default=0.0, help="min-p sampling (0 = off)")
+    ap.add_argument("--presence-penalty", type=float, default=0.0, help="on every request (0 = off)")
+    ap.add_argument("--frequency-penalty", type=float, default=0.0, help="on every request (0 = off)")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0, help="on every request (1 = off)")
     ap.add_argument("--quantization", choices=["fp8"], default=None)
     ap.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto")
     ap.add_argument("--enable-prefix-caching", action="store_true",
@@ -78,7 +81,8 @@ def main():
     vocab = m.cfg.vocab_size
     rng = np.random.default_rng(0)
     sp = SamplingParams(max_tokens=args.output_len, temperature=args.temperature, top_p=args.top_p, top_k=args.top_k,
-                        min_p=args.min_p, ignore_eos=True)
+                        min_p=args.min_p, ignore_eos=True, presence_penalty=args.presence_penalty,
+                        frequency_penalty=args.frequency_penalty, repetition_penalty=args.repetition_penalty)
 
     shared = rng.integers(10, vocab - 10, size=args.shared_prefix_len).tolist() if args.shared_prefix_len else []
 
@@ -118,6 +122,8 @@ def main():
         "data": "synthetic prompts (uniform random token ids), random-init weights",
         "num_prompts": n, "input_len": args.input_len, "output_len": args.output_len,
         "temperature": args.temperature, "top_p": args.top_p, "top_k": args.top_k, "min_p": args.min_p,
+        "presence_penalty": args.presence_penalty, "frequency_penalty": args.frequency_penalty,
+        "repetition_penalty": args.repetition_penalty,
         "max_batch": eng.max_batch, "elapsed_s": round(elapsed, 3),
         "output_tokens_per_s": round(out_tokens / elapsed, 1),
         "total_tokens_per_s": round((in_tokens + out_tokens) / elapsed, 1),

@@ -42,6 +42,10 @@ hipError_t dsa_sample_masked(const void*, long, int, int, const float*, const in
                              float*, hipStream_t);
 hipError_t dsa_top_logprobs(const void*, long, int, int, const float*, const float*, const int*, int*, float*,
                             hipStream_t);
+int dsa_logit_bias_max();
+hipError_t dsa_apply_penalties(void*, long, int, int, const int*, int, const int*, const float*, const float*,
+                               const float*, const float*, const int*, const float*, const int*, hipStream_t);
+hipError_t dsa_penalties_update(int*, int, int, const int*, const int*, int, hipStream_t);
 hipError_t dsa_paged_prefill(const void*, long, long, const void*, const void*, const int*, int, int, const int*,
                              const int*, const int*, void*, int, int, int, int, float, int, float, float,
                              hipStream_t);
@@ -1043,6 +1047,54 @@ void top_logprobs(torch::Tensor logits, torch::Tensor temps, torch::Tensor tau, 
         "top_logprobs");
 }
 
+// --- sampling penalties (penalties.hip): every tensor is caller-owned, nothing is allocated or read back ---
+// state int32 [slots, V]: 2 * (times generated) + (in the prompt), one row per sequence that asked
+void check_penalty_state(const torch::Tensor& state, int64_t V) {
+  check_i32(state, "state");
+  TORCH_CHECK(state.dim() == 2 && state.size(0) >= 1 && state.size(1) == V, "state must be int32 [slots, V]");
+}
+
+// logits rewritten in place for the rows with slot >= 0 (slot, rep, inv_rep, freq, pres: per row;
+// bias_ids / bias_vals [slots, logit_bias_max] and bias_n [slots]: per slot)
+void apply_penalties(torch::Tensor logits, torch::Tensor state, torch::Tensor slot, torch::Tensor rep,
+                     torch::Tensor inv_rep, torch::Tensor freq, torch::Tensor pres, torch::Tensor bias_ids,
+                     torch::Tensor bias_vals, torch::Tensor bias_n) {
+  check_logits(logits);
+  const int64_t rows = logits.size(0), V = logits.size(1), N = dsa_logit_bias_max();
+  check_penalty_state(state, V);
+  const int64_t slots = state.size(0);
+  check_i32_rows(slot, rows, "slot");
+  check_f32_rows(rep, rows, "rep");
+  check_f32_rows(inv_rep, rows, "inv_rep");
+  check_f32_rows(freq, rows, "freq");
+  check_f32_rows(pres, rows, "pres");
+  check_i32(bias_ids, "bias_ids");
+  TORCH_CHECK(bias_ids.dim() == 2 && bias_ids.size(0) == slots && bias_ids.size(1) == N,
+              "bias_ids must be int32 [slots, ", N, "]");
+  TORCH_CHECK(bias_vals.is_cuda() && bias_vals.scalar_type() == torch::kFloat32 && bias_vals.is_contiguous() &&
+                  bias_vals.dim() == 2 && bias_vals.size(0) == slots && bias_vals.size(1) == N,
+              "bias_vals must be fp32 [slots, ", N, "]");
+  check_i32_rows(bias_n, slots, "bias_n");
+  TORCH_CHECK(rows <= 65535, "apply_penalties: at most 65535 rows");
+  check(dsa_apply_penalties(logits.data_ptr(), logits.stride(0), (int)rows, (int)V, state.data_ptr<int>(),
+                            (int)slots, slot.data_ptr<int>(), rep.data_ptr<float>(), inv_rep.data_ptr<float>(),
+                            freq.data_ptr<float>(), pres.data_ptr<float>(), bias_ids.data_ptr<int>(),
+                            bias_vals.data_ptr<float>(), bias_n.data_ptr<int>(), stream()),
+        "apply_penalties");
+}
+
+// state[slot[r]][tokens[r]] += 2 for the rows with slot >= 0 (slots unique among the rows)
+void penalties_update(torch::Tensor state, torch::Tensor slot, torch::Tensor tokens) {
+  check_i32(state, "state");
+  TORCH_CHECK(state.dim() == 2 && state.size(0) >= 1 && state.size(1) >= 1, "state must be int32 [slots, V]");
+  const int64_t rows = slot.numel();
+  check_i32_rows(slot, rows, "slot");
+  check_i32_rows(tokens, rows, "tokens");
+  check(dsa_penalties_update(state.data_ptr<int>(), (int)state.size(0), (int)state.size(1), slot.data_ptr<int>(),
+                             tokens.data_ptr<int>(), (int)rows, stream()),
+        "penalties_update");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1125,4 +1177,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_masked", &sample_masked);
   m.def("top_logprobs", &top_logprobs);
   m.def("top_logprobs_max", &dsa_top_logprobs_max);
+  m.def("apply_penalties", &apply_penalties);
+  m.def("penalties_update", &penalties_update);
+  m.def("logit_bias_max", &dsa_logit_bias_max);
 }

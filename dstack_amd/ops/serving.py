@@ -1,8 +1,9 @@
 """Serving ops: paged KV cache writes, paged decode attention, paged-prefix prefill attention and
 sampling.
 
-HIP kernels in ``csrc/paged_attn.hip``, ``csrc/paged_prefill.hip`` and ``csrc/sampler.hip`` (top-k /
-top-p / min-p truncation, top-N log-probabilities) for ROCm tensors; the PyTorch
+HIP kernels in ``csrc/paged_attn.hip``, ``csrc/paged_prefill.hip``, ``csrc/sampler.hip`` (top-k /
+top-p / min-p truncation, top-N log-probabilities) and ``csrc/penalties.hip`` (presence / frequency /
+repetition penalties, logit_bias) for ROCm tensors; the PyTorch
 functions here are the CPU path of the engine and the fp32 references the GPU tests compare against.
 
 Cache layout (per layer): ``k_cache [pages, KVH, PAGE, 128]`` token-major and
@@ -379,6 +380,137 @@ def sample_filtered(logits: torch.Tensor, temps: torch.Tensor, seeds: torch.Tens
         return tokens, logprobs, None, None
     top_ids, top_lps = top_logprobs(logits, temps, tau, top_n, top_ids, top_lps)
     return tokens, logprobs, top_ids, top_lps
+
+
+# ----------------------------------------------------------------------------------------------
+# Sampling penalties (presence / frequency / repetition) and logit_bias: csrc/penalties.hip
+# ----------------------------------------------------------------------------------------------
+LOGIT_BIAS_MAX = 300
+
+
+def alloc_penalty_state(slots: int, vocab: int, device=None):
+    """``(state, bias_ids, bias_vals, bias_n)`` for ``slots`` sequences: ``state`` int32 [slots, V]
+    holds ``2 * c[v] + in_prompt[v]`` (``c``: how often the sequence generated token v), the bias
+    list of a slot is ``bias_ids`` int32 / ``bias_vals`` fp32 [slots, LOGIT_BIAS_MAX] with ``bias_n``
+    int32 [slots] entries in use."""
+    return (torch.zeros(slots, vocab, dtype=torch.int32, device=device),
+            torch.zeros(slots, LOGIT_BIAS_MAX, dtype=torch.int32, device=device),
+            torch.zeros(slots, LOGIT_BIAS_MAX, dtype=torch.float32, device=device),
+            torch.zeros(slots, dtype=torch.int32, device=device))
+
+
+def check_logit_bias(logit_bias, vocab: int) -> dict:
+    """``logit_bias`` as ``{token id (int): bias (float)}``: at most LOGIT_BIAS_MAX entries, keys ints
+    or strings of ints in ``[0, vocab)``, values numbers in [-100, 100].  Raises ValueError otherwise."""
+    if not logit_bias:
+        return {}
+    if not isinstance(logit_bias, dict):
+        raise ValueError("logit_bias must be an object mapping token ids to numbers")
+    if len(logit_bias) > LOGIT_BIAS_MAX:
+        raise ValueError(f"logit_bias may hold at most {LOGIT_BIAS_MAX} entries, got {len(logit_bias)}")
+    out = {}
+    for k, v in logit_bias.items():
+        try:
+            if isinstance(k, (bool, float)):
+                raise ValueError
+            t = int(k)
+        except (TypeError, ValueError):
+            raise ValueError(f"logit_bias key {k!r} is not a token id") from None
+        if not 0 <= t < vocab:
+            raise ValueError(f"logit_bias token id {t} is outside [0, {vocab})")
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not -100.0 <= v <= 100.0:
+            raise ValueError(f"logit_bias value for token {t} must be a number in [-100, 100], got {v!r}")
+        if t in out:
+            raise ValueError(f"logit_bias names token {t} twice")
+        out[t] = float(v)
+    return out
+
+
+def penalties_fill(state: torch.Tensor, bias_ids: torch.Tensor, bias_vals: torch.Tensor, bias_n: torch.Tensor,
+                   slot: int, prompt_ids, output_ids, logit_bias: dict | None = None) -> None:
+    """Rebuild slot ``slot`` from a request: its state row from the prompt and the generated tokens,
+    its bias list from ``logit_bias`` ({int id: number}, validated by :func:`check_logit_bias`).
+    Ordinary torch ops -- this runs once per admission, not per step."""
+    dev = state.device
+    row = state[slot]
+    row.zero_()
+    if len(prompt_ids):
+        row[torch.unique(torch.as_tensor(list(prompt_ids), dtype=torch.int64)).to(dev)] = 1
+    if len(output_ids):
+        ids, cnt = torch.unique(torch.as_tensor(list(output_ids), dtype=torch.int64), return_counts=True)
+        row.index_add_(0, ids.to(dev), (2 * cnt).to(torch.int32).to(dev))
+    items = sorted((logit_bias or {}).items())
+    n = len(items)
+    assert n <= LOGIT_BIAS_MAX, n
+    bias_n[slot] = n
+    if n:
+        bias_ids[slot, :n] = torch.tensor([k for k, _ in items], dtype=torch.int32).to(dev)
+        bias_vals[slot, :n] = torch.tensor([v for _, v in items], dtype=torch.float32).to(dev)
+
+
+def inv_rep_of(rep: torch.Tensor) -> torch.Tensor:
+    """fp32 ``1 / r``, the one division of the repetition penalty (done on the host, not in the kernel)."""
+    return 1.0 / rep.to(torch.float32)
+
+
+def apply_penalties(logits: torch.Tensor, state: torch.Tensor, slot: torch.Tensor, rep: torch.Tensor,
+                    inv_rep: torch.Tensor, freq: torch.Tensor, pres: torch.Tensor, bias_ids: torch.Tensor,
+                    bias_vals: torch.Tensor, bias_n: torch.Tensor) -> torch.Tensor:
+    """Rewrite, in place, the logits of every row r with ``slot[r] >= 0`` (int32; -1: the row asks for
+    nothing and is not written).  With ``s = state[slot[r]]``, ``c = s >> 1``, ``seen = s != 0``, per
+    element in fp32, each step one correctly rounded operation:
+
+    1. repetition (``rep[r] != 1`` and seen): ``x = x * inv_rep[r] if x > 0 else x * rep[r]``;
+    2. frequency: ``x = x - freq[r] * float(c)``;
+    3. presence (``c > 0``): ``x = x - pres[r]``;
+    4. bias (the ``bias_n`` ids of the slot's list): ``x = x + bias``;
+    5. one rounding to the logits' dtype.  A -inf logit stays -inf.
+
+    ``rep`` / ``inv_rep`` / ``freq`` / ``pres``: fp32 [rows].  On ROCm tensors nothing is allocated or
+    read back (hipGraph-capturable).  Returns ``logits``."""
+    if _ext.use_hip(logits):
+        _ext.require().apply_penalties(logits, state, slot, rep, inv_rep, freq, pres, bias_ids, bias_vals, bias_n)
+        return logits
+    rows = slot >= 0
+    if bool(rows.any()):
+        ref = apply_penalties_ref(logits, state, slot, rep, inv_rep, freq, pres, bias_ids, bias_vals, bias_n)
+        logits[rows] = ref[rows]
+    return logits
+
+
+def apply_penalties_ref(logits, state, slot, rep, inv_rep, freq, pres, bias_ids, bias_vals, bias_n) -> torch.Tensor:
+    """Reference of :func:`apply_penalties`: the fp32 steps as separate torch operations on the CPU.
+    Returns a new tensor like ``logits`` (rows with ``slot < 0`` are copies)."""
+    out = logits.detach().cpu().clone()
+    state, bias_ids, bias_vals, bias_n = state.cpu(), bias_ids.cpu(), bias_vals.cpu(), bias_n.cpu()
+    rep, inv_rep, freq, pres = (t.detach().float().cpu() for t in (rep, inv_rep, freq, pres))
+    for i, s in enumerate(slot.cpu().tolist()):
+        if s < 0:
+            continue
+        x = out[i].float()
+        c = state[s] >> 1
+        r, ir, f, p = rep[i], inv_rep[i], freq[i], pres[i]  # 0-dim fp32 tensors: every product stays fp32
+        if r != 1:
+            x = torch.where(state[s] != 0, torch.where(x > 0, x * ir, x * r), x)
+        m = f * c.float()
+        x = x - m
+        x = torch.where(c > 0, x - p, x)
+        n = int(bias_n[s])
+        if n:
+            ids = bias_ids[s, :n].long()
+            x[ids] = x[ids] + bias_vals[s, :n]
+        out[i] = x.to(out.dtype)
+    return out.to(logits.device)
+
+
+def penalties_update(state: torch.Tensor, slot: torch.Tensor, tokens: torch.Tensor) -> None:
+    """Record the sampled ``tokens`` (int32 [rows]): ``state[slot[r]][tokens[r]] += 2`` for the rows
+    with ``slot[r] >= 0``.  Slots are unique among the rows of a step."""
+    if _ext.use_hip(state):
+        _ext.require().penalties_update(state, slot, tokens)
+        return
+    rows = slot >= 0
+    state[slot[rows].long(), tokens[rows].long()] += 2
 
 
 # ----------------------------------------------------------------------------------------------

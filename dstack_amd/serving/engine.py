@@ -47,6 +47,31 @@ class SamplingParams:
     seed: int | None = None
     ignore_eos: bool = False
     stop_token_ids: tuple = ()
+    # adjustments of the logits in front of truncation and the draw (ops.serving.apply_penalties)
+    presence_penalty: float = 0.0  # subtracted from tokens generated so far; [-2, 2]
+    frequency_penalty: float = 0.0  # times the token's count among the generated tokens; [-2, 2]
+    repetition_penalty: float = 1.0  # divides (x > 0) or multiplies the logits of prompt and generated tokens; (0, 2]
+    logit_bias: dict | None = None  # {token id: bias in [-100, 100]}, at most LOGIT_BIAS_MAX entries
+
+    @property
+    def wants_penalties(self) -> bool:
+        return (self.presence_penalty != 0.0 or self.frequency_penalty != 0.0 or self.repetition_penalty != 1.0
+                or bool(self.logit_bias))
+
+
+def check_penalties(params: SamplingParams, vocab: int) -> dict:
+    """Validate the penalty fields of ``params`` (ValueError outside the accepted ranges) and return
+    its ``logit_bias`` as ``{int token id: float}``."""
+    def num(name, lo, hi, open_lo=False):
+        v = getattr(params, name)
+        ok = not isinstance(v, bool) and isinstance(v, (int, float)) and (lo < v if open_lo else lo <= v) and v <= hi
+        if not ok:
+            raise ValueError(f"{name} must be in {'(' if open_lo else '['}{lo}, {hi}], got {v!r}")
+
+    num("presence_penalty", -2, 2)
+    num("frequency_penalty", -2, 2)
+    num("repetition_penalty", 0, 2, open_lo=True)
+    return sops.check_logit_bias(params.logit_bias, vocab)
 
 
 @dataclass
@@ -65,6 +90,7 @@ class Request:
     on_event: object = None
     seed: int = 0
     cached_tokens: int = 0  # prompt tokens taken from the prefix cache at admission
+    logit_bias: dict = field(default_factory=dict)  # params.logit_bias, validated: {int token id: float}
 
     @property
     def all_ids(self):
@@ -166,15 +192,38 @@ class LLMEngine:
         self.s_top_ids = torch.full((B, sops.TOP_LOGPROBS_MAX), -1, **i32)
         self.s_top_lps = torch.full((B, sops.TOP_LOGPROBS_MAX), float("-inf"), dtype=torch.float32, device=dev)
         self._filter_rows_set = 0  # leading rows of the four parameter buffers that may hold a request's values
+        # penalties and logit_bias: one state row and bias list per running sequence that asked (a
+        # request takes a slot when its prompt is sampled and gives it back when it finishes or is
+        # preempted), and per-row parameters (padding rows and rows that ask for nothing: slot -1)
+        # (tensor parallel: only the leader samples, so only the leader holds state)
+        self.p_state, self.p_bias_ids, self.p_bias_vals, self.p_bias_n = sops.alloc_penalty_state(
+            B if self.leader else 1, self.model.cfg.vocab_size, dev)
+        self.s_pen_slot = torch.full((B,), -1, **i32)
+        self.s_pen = torch.empty(4, B, dtype=torch.float32, device=dev)  # rows: rep, 1 / rep, freq, pres
+        self._reset_penalty_rows(B)
+        self._pen_free = list(range(B - 1, -1, -1))
+        self._pen_slots: dict[int, int] = {}  # request id -> slot
         self._ws = {b: sops.DecodeWorkspace(b, self.model.H, self.model.KVH, W, dev) for b in self.buckets}
+
+    def _reset_penalty_rows(self, m: int):
+        self.s_pen_slot[:m].fill_(-1)
+        self.s_pen[:2, :m].fill_(1.0)
+        self.s_pen[2:, :m].zero_()
+        self._pen_rows_set = 0  # leading rows of the penalty parameter buffers that may hold a request's values
+
+    def _apply_penalties(self, logits, slot, pen):
+        return sops.apply_penalties(logits, self.p_state, slot, pen[0], pen[1], pen[2], pen[3], self.p_bias_ids,
+                                    self.p_bias_vals, self.p_bias_n)
 
     def _decode_body(self, b: int):
         logits = self.model.decode(self.s_tokens[:b], self.s_pos[:b], self.s_slots[:b], self.s_tables[:b],
                                    self.s_ctx[:b], ws=self._ws[b])
+        self._apply_penalties(logits, self.s_pen_slot[:b], self.s_pen[:, :b])
         sops.sample_filtered(logits, self.s_temps[:b], self.s_seeds[:b], self.s_steps[:b], self.s_top_k[:b],
                              self.s_top_p[:b], self.s_min_p[:b], self.s_out_tok[:b], self.s_out_lp[:b],
                              top_n=self.s_top_n[:b], top_ids=self.s_top_ids[:b], top_lps=self.s_top_lps[:b],
                              tau=self.s_tau[:b])
+        sops.penalties_update(self.p_state, self.s_pen_slot[:b], self.s_out_tok[:b])
         return logits
 
     def capture_graphs(self):
@@ -189,6 +238,7 @@ class LLMEngine:
         self.s_min_p.zero_()
         self.s_top_n.zero_()
         self._filter_rows_set = 0
+        self._reset_penalty_rows(self.max_batch)
         torch.cuda.synchronize(self.device)
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
@@ -222,9 +272,10 @@ class LLMEngine:
             raise ValueError(f"min_p must be in [0, 1], got {params.min_p}")
         if not 0 <= params.top_logprobs <= sops.TOP_LOGPROBS_MAX:
             raise ValueError(f"top_logprobs must be in [0, {sops.TOP_LOGPROBS_MAX}], got {params.top_logprobs}")
+        logit_bias = check_penalties(params, vocab)
         rid = next(self._ids)
         seed = params.seed if params.seed is not None else (rid * 7919 + 17)
-        req = Request(rid, list(prompt_ids), params, on_event=on_event, seed=int(seed))
+        req = Request(rid, list(prompt_ids), params, on_event=on_event, seed=int(seed), logit_bias=logit_bias)
         with self._lock:
             self.requests[rid] = req
             self._pending.append(req)
@@ -258,6 +309,7 @@ class LLMEngine:
                 self.sched.add(req.id, len(req.prompt_ids), len(req.prompt_ids) + req.params.max_tokens)
         for rid in aborted:
             self.sched.finish(rid)
+            self._release_penalty_slot(rid)
             self._emit(self.requests.pop(rid, None), None, True)
 
     def _emit(self, req, token, finished):
@@ -270,6 +322,7 @@ class LLMEngine:
         plan = self.sched.schedule(False)
         for rid in plan["preempted"]:
             self.stats["preemptions"] += 1
+            self._release_penalty_slot(rid)  # rebuilt when its recompute prefill is sampled
         kind = plan["kind"]
         if kind == "idle":
             return 0
@@ -328,6 +381,7 @@ class LLMEngine:
             if reason:
                 req.finished, req.finish_reason, req.finished_at = True, reason, now
                 self.sched.finish(req.id)
+                self._release_penalty_slot(req.id)
             self._emit(req, tok, req.finished)
             if req.finished:
                 self.requests.pop(req.id, None)
@@ -364,6 +418,43 @@ class LLMEngine:
             self.s_min_p[:m].zero_()
             self.s_top_n[:m].zero_()
 
+    def _release_penalty_slot(self, rid: int):
+        slot = self._pen_slots.pop(rid, None)
+        if slot is not None:
+            self._pen_free.append(slot)
+
+    def _take_penalty_slot(self, req) -> int:
+        """A free slot for ``req``, its state row and bias list rebuilt from the request (a
+        readmission after preemption also counts the tokens generated so far)."""
+        slot = self._pen_free.pop()  # at most max_batch sequences run and there are max_batch slots
+        self._pen_slots[req.id] = slot
+        sops.penalties_fill(self.p_state, self.p_bias_ids, self.p_bias_vals, self.p_bias_n, slot, req.prompt_ids,
+                            req.output_ids, req.logit_bias)
+        return slot
+
+    def _penalty_rows(self, reqs, rows: int | None = None):
+        """slot int32 [m] and (rep, 1 / rep, freq, pres) fp32 [4, m] of the requests, padded with inert
+        rows up to ``rows``; a request without a slot asks for nothing."""
+        pad = max(0, (rows or 0) - len(reqs))
+        slot = torch.tensor([self._pen_slots.get(r.id, -1) for r in reqs] + [-1] * pad, dtype=torch.int32)
+        p = [r.params if r.id in self._pen_slots else SamplingParams() for r in reqs]
+        rep = torch.tensor([q.repetition_penalty for q in p] + [1.0] * pad, dtype=torch.float32)
+        freq = torch.tensor([q.frequency_penalty for q in p] + [0.0] * pad, dtype=torch.float32)
+        pres = torch.tensor([q.presence_penalty for q in p] + [0.0] * pad, dtype=torch.float32)
+        return slot, torch.stack([rep, sops.inv_rep_of(rep), freq, pres])
+
+    def _stage_penalties(self, reqs, b: int):
+        """Stage penalty slots and parameters into the static buffers, as ``_stage_filters`` does:
+        steps where no request holds a slot (the common case) copy nothing."""
+        if self._pen_slots and any(r.id in self._pen_slots for r in reqs):
+            m = max(b, self._pen_rows_set)
+            slot, pen = self._penalty_rows(reqs, m)
+            self.s_pen_slot[:m].copy_(slot, non_blocking=True)
+            self.s_pen[:, :m].copy_(pen, non_blocking=True)
+            self._pen_rows_set = len(reqs)
+        elif self._pen_rows_set:
+            self._reset_penalty_rows(self._pen_rows_set)
+
     @staticmethod
     def _tops(reqs, ids, lps):
         """The top-N outputs on the host, copied only in steps where some request asked for them."""
@@ -374,7 +465,18 @@ class LLMEngine:
     def _sample(self, logits, reqs):
         temps, seeds, steps = (t.to(self.device) for t in self._seed_rows(reqs))
         top_k, top_p, min_p, top_n = (t.to(self.device) for t in self._filter_rows(reqs))
+        # the prefill path: a request that asks for a penalty or a bias takes its slot here, and the
+        # same adjustment as in the decode graph runs eagerly around the sampler
+        for r in reqs:
+            if r.params.wants_penalties and r.id not in self._pen_slots:
+                self._take_penalty_slot(r)
+        slot = None
+        if any(r.id in self._pen_slots for r in reqs):
+            slot, pen = (t.to(self.device) for t in self._penalty_rows(reqs))
+            self._apply_penalties(logits, slot, pen)
         tok, lp, ids, tlp = sops.sample_filtered(logits, temps, seeds, steps, top_k, top_p, min_p, top_n=top_n)
+        if slot is not None:
+            sops.penalties_update(self.p_state, slot, tok)
         return tok.tolist(), lp.tolist(), self._tops(reqs, ids, tlp)
 
     def _decode(self, plan, reqs):
@@ -394,6 +496,7 @@ class LLMEngine:
             self.s_seeds[:n].copy_(seeds, non_blocking=True)
             self.s_steps[:n].copy_(steps, non_blocking=True)
             self._stage_filters(reqs, b)
+            self._stage_penalties(reqs, b)
             if b > n:
                 self.s_slots[n:b].fill_(-1)
                 self.s_ctx[n:b].zero_()
@@ -508,6 +611,7 @@ class LLMEngine:
                     self._pending.clear()
                 for r in victims:
                     self.sched.finish(r.id)
+                    self._release_penalty_slot(r.id)
                     r.finished, r.finish_reason = True, f"error: {e}"
                     self._emit(r, None, True)
 

@@ -23,7 +23,7 @@ from fastapi import FastAPI, HTTPException, Request
 from fastapi.responses import JSONResponse, PlainTextResponse, StreamingResponse
 
 from dstack_amd.ops.serving import TOP_LOGPROBS_MAX
-from dstack_amd.serving.engine import LLMEngine, SamplingParams
+from dstack_amd.serving.engine import LLMEngine, SamplingParams, check_penalties
 from dstack_amd.serving.tokenizer import load_tokenizer
 
 
@@ -121,11 +121,20 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
         min_p = _num(body, "min_p", float, 0.0)
         if not 0.0 <= min_p <= 1.0:
             raise _bad("min_p must be between 0 and 1")
-        return SamplingParams(max_tokens=mt, temperature=1.0 if t is None else float(t),
-                              top_p=float(body.get("top_p") or 1.0), top_k=int(body.get("top_k") or 0),
-                              min_p=min_p, top_logprobs=_top_logprobs(body, chat),
-                              seed=body.get("seed"), ignore_eos=bool(body.get("ignore_eos", False)),
-                              stop_token_ids=stop_ids)
+        sp = SamplingParams(max_tokens=mt, temperature=1.0 if t is None else float(t),
+                            top_p=float(body.get("top_p") or 1.0), top_k=int(body.get("top_k") or 0),
+                            min_p=min_p, top_logprobs=_top_logprobs(body, chat),
+                            seed=body.get("seed"), ignore_eos=bool(body.get("ignore_eos", False)),
+                            stop_token_ids=stop_ids,
+                            presence_penalty=_num(body, "presence_penalty", float, 0.0),
+                            frequency_penalty=_num(body, "frequency_penalty", float, 0.0),
+                            repetition_penalty=_num(body, "repetition_penalty", float, 1.0),
+                            logit_bias=body.get("logit_bias"))
+        try:
+            sp.logit_bias = check_penalties(sp, engine.model.cfg.vocab_size) or None
+        except ValueError as e:
+            raise _bad(str(e)) from e
+        return sp
 
     def _submit(ids, params, stop):
         loop = asyncio.get_running_loop()

@@ -11,7 +11,13 @@ Per row count it times (GPU time, hip events, median of ``--iters`` after warm-u
 - ``filtered``: ``ops.serving.sample_filtered`` with top-p on every row (threshold + masked draw +
   the idle top-N kernel, as the decode graph runs them);
 - ``unfiltered`` against ``sample``: ``sample_filtered`` with nothing asked for, and the plain
-  ``sample`` kernel.
+  ``sample`` kernel;
+- ``idle_chain``: what the decode graph runs when no request asks for a penalty -- ``apply_penalties``
+  with every slot -1, ``sample_filtered`` with nothing asked for, ``penalties_update`` -- to set beside
+  ``unfiltered``; ``noop_launch``: one launch that does nothing (``penalties_update``, every slot -1);
+- ``penalised``: ``apply_penalties`` alone with every row penalised (repetition, frequency, presence),
+  without and with 300 ``logit_bias`` entries per row, and the rate it reaches counting 8 B per
+  element (2 B + 4 B read, 2 B written); ``penalised_chain``: the same in front of the sampler.
 
 Prints one JSON line per row count.
 """
@@ -92,6 +98,37 @@ def main():
             "device": torch.cuda.get_device_name(0),
         }
         res["filtered_speedup"] = round(res["python_filter_ms"] / res["filtered_ms"], 1)
+
+        # penalties / logit_bias in front of the sampler (csrc/penalties.hip), as the decode graph chains them
+        V = args.vocab
+        state, bias_ids, bias_vals, bias_n = sops.alloc_penalty_state(R, V, dev)
+        state.copy_(torch.randint(0, 4, (R, V), device=dev, dtype=torch.int32))
+        bias_ids.copy_(torch.stack([torch.randperm(V, device=dev)[: sops.LOGIT_BIAS_MAX] for _ in range(R)]))
+        bias_vals.uniform_(-5, 5)
+        idle = torch.full((R,), -1, device=dev, dtype=torch.int32)
+        slot = torch.arange(R, device=dev, dtype=torch.int32).flip(0)
+        rep = torch.full((R,), 1.1, device=dev)
+        freq, pres = torch.full((R,), 0.5, device=dev), torch.full((R,), 0.25, device=dev)
+        pen = logits.clone()  # (rewritten in place by every call; the time does not depend on the values)
+
+        inv = sops.inv_rep_of(rep)
+
+        def apply(s):
+            sops.apply_penalties(pen, state, s, rep, inv, freq, pres, bias_ids, bias_vals, bias_n)
+
+        def chain(s):
+            apply(s)
+            sops.sample_filtered(pen, temps, seeds, steps, zero_i, ones, zeros, **out)
+            sops.penalties_update(state, s, out["tokens"])
+
+        res["idle_chain_ms"] = round(gpu_ms(lambda: chain(idle), args.iters), 4)
+        res["noop_launch_ms"] = round(gpu_ms(lambda: sops.penalties_update(state, idle, out["tokens"]), args.iters), 4)
+        res["penalised_ms"] = round(gpu_ms(lambda: apply(slot), args.iters), 4)
+        res["penalised_chain_ms"] = round(gpu_ms(lambda: chain(slot), args.iters), 4)
+        bias_n.fill_(sops.LOGIT_BIAS_MAX)
+        res["penalised_bias300_ms"] = round(gpu_ms(lambda: apply(slot), args.iters), 4)
+        for k in ("penalised_ms", "penalised_bias300_ms"):  # 2 B + 4 B read, 2 B written per element
+            res[k.replace("_ms", "_tbps")] = round(R * V * 8 / (res[k] * 1e-3) / 1e12, 3)
         print(json.dumps(res), flush=True)
 
 
