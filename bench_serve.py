@@ -6,6 +6,8 @@ latency of one model replica on one GPU, random-init weights, synthetic prompts.
     python bench_serve.py --model llama-3-70b --latency --input-len 32000 --output-len 128
     python bench_serve.py --model llama-3-8b --num-prompts 64 --input-len 2048 --output-len 16 \
         --shared-prefix-len 1536 --enable-prefix-caching
+    python bench_serve.py --model llama-3-8b --num-loras 8 --lora-rank 16      # requests round-robin over 8 adapters
+    python bench_serve.py --model llama-3-8b --num-loras 8 --lora-idle         # adapters loaded, none requested
 
 Throughput mode submits every prompt at t=0 (like ``vllm benchmark_throughput``) and reports
 output and total tokens/s, TTFT / time-per-output-token percentiles, and the engine's prefill and
@@ -58,7 +60,15 @@ def main():
     ap.add_argument("--shared-prefix-len", type=int, default=0,
                     help="the first N tokens of every prompt are identical (a system prompt / template); the rest "
                          "differ per prompt")
+    ap.add_argument("--num-loras", type=int, default=0,
+                    help="serve N random LoRA adapters (written to a temporary directory) and assign the requests "
+                         "to them round-robin")
+    ap.add_argument("--lora-rank", type=int, default=16, help="rank of the random adapters")
+    ap.add_argument("--lora-idle", action="store_true",
+                    help="with --num-loras: load the adapters but send every request to the base model")
     args = ap.parse_args()
+    if args.lora_idle and not args.num_loras:
+        ap.error("--lora-idle needs --num-loras")
     if not 0 <= args.shared_prefix_len <= args.input_len:
         ap.error("--shared-prefix-len must be within --input-len")
 
@@ -68,11 +78,25 @@ def main():
     from dstack_amd.serving.engine import LLMEngine, SamplingParams
 
     max_len = args.max_model_len or max(args.input_len + args.output_len + 64, 2048)
+    lora_modules, lora_dir = None, None
+    if args.num_loras:
+        import tempfile
+
+        from dstack_amd.serving.lora import write_random_adapter
+        from dstack_amd.serving.model import load_spec
+
+        lora_dir = tempfile.TemporaryDirectory(prefix="bench_serve_lora_")
+        cfg = load_spec(args.model).cfg
+        lora_modules = {f"lora-{i}": write_random_adapter(os.path.join(lora_dir.name, f"lora-{i}"), cfg,
+                                                          args.lora_rank, seed=i) for i in range(args.num_loras)}
     t0 = time.perf_counter()
     eng = LLMEngine.from_model(args.model, max_model_len=max_len, max_batch=1 if args.latency else args.max_batch,
                                max_prefill_tokens=args.max_prefill_tokens, use_graphs=not args.no_graphs and None,
                                quantization=args.quantization, kv_cache_dtype=args.kv_cache_dtype,
-                               enable_prefix_caching=args.enable_prefix_caching)
+                               enable_prefix_caching=args.enable_prefix_caching, lora_modules=lora_modules,
+                               max_lora_rank=max(args.lora_rank, 8))
+    if lora_dir is not None:
+        lora_dir.cleanup()  # the adapters are in HBM now
     t_load = time.perf_counter() - t0
     t0 = time.perf_counter()
     eng.capture_graphs()
@@ -97,13 +121,15 @@ def main():
     torch.cuda.synchronize() if torch.cuda.is_available() else None
 
     n = args.repeats if args.latency else args.num_prompts
+    names = list(lora_modules) if lora_modules and not args.lora_idle else [None]
+    lora = [names[i % len(names)] for i in range(n)]
     t0 = time.perf_counter()
     if args.latency:
         reqs = []
-        for p in prompts(n):
-            reqs += eng.generate([p], sp)
+        for p, l in zip(prompts(n), lora):
+            reqs += eng.generate([p], sp, lora=l)
     else:
-        reqs = eng.generate(prompts(n), sp)
+        reqs = eng.generate(prompts(n), sp, lora=lora)
     elapsed = time.perf_counter() - t0
     out_tokens = sum(len(r.output_ids) for r in reqs)
     in_tokens = sum(len(r.prompt_ids) for r in reqs)
@@ -132,6 +158,8 @@ def main():
         "prefill_tokens_per_s": round(st["prefill_tokens"] / st["prefill_s"], 1) if st["prefill_s"] else None,
         # prompt tokens admitted (computed + served from the prefix cache) per second of prefill steps
         "prompt_tokens_per_prefill_s": round((st["prefill_tokens"] + hits) / st["prefill_s"], 1) if st["prefill_s"] else None,
+        "num_loras": args.num_loras, "lora_rank": args.lora_rank if args.num_loras else None,
+        "lora_idle": args.lora_idle, "lora_requests": sum(eng.lora_requests.values()),
         "prefix_caching": args.enable_prefix_caching, "shared_prefix_len": args.shared_prefix_len,
         "prefix_hit_tokens": hits, "prefill_s": round(st["prefill_s"], 4),
         "decode_tokens_per_s": round(st["decode_tokens"] / st["decode_s"], 1) if st["decode_s"] else None,

@@ -46,6 +46,11 @@ int dsa_logit_bias_max();
 hipError_t dsa_apply_penalties(void*, long, int, int, const int*, int, const int*, const float*, const float*,
                                const float*, const float*, const int*, const float*, const int*, hipStream_t);
 hipError_t dsa_penalties_update(int*, int, int, const int*, const int*, int, hipStream_t);
+bool dsa_lora_shrink_supported(int, int, int, int);
+bool dsa_lora_expand_supported(int, int, int, int, int);
+hipError_t dsa_lora_shrink(const void*, long, const void*, const int*, float*, int, int, int, int, hipStream_t);
+hipError_t dsa_lora_expand(const float*, const void*, const int*, void*, long, int, int, int, int, int, const int*,
+                           hipStream_t);
 hipError_t dsa_paged_prefill(const void*, long, long, const void*, const void*, const int*, int, int, const int*,
                              const int*, const int*, void*, int, int, int, int, float, int, float, float,
                              hipStream_t);
@@ -1095,6 +1100,59 @@ void penalties_update(torch::Tensor state, torch::Tensor slot, torch::Tensor tok
         "penalties_update");
 }
 
+// --- batched multi-LoRA (lora.hip): every tensor is caller-owned, nothing is allocated or read back ---
+bool lora_shrink_supported(int64_t T, int64_t S, int64_t L, int64_t K) {
+  return dsa_lora_shrink_supported((int)T, (int)S, (int)L, (int)K);
+}
+
+bool lora_expand_supported(int64_t T, int64_t S, int64_t nsl, int64_t R, int64_t N) {
+  return dsa_lora_expand_supported((int)T, (int)S, (int)nsl, (int)R, (int)N);
+}
+
+// t [T, L] fp32 (rows with idx >= 0) = x [T, K] @ A[idx]^T; A bf16 [S, L, K], idx int32 [T]
+void lora_shrink(torch::Tensor x, torch::Tensor A, torch::Tensor idx, torch::Tensor t) {
+  check_rows(x, "lora_shrink x");
+  check_bf16(A, "A");
+  TORCH_CHECK(A.dim() == 3 && A.size(2) == x.size(1), "lora_shrink: A must be [S, L, K]");
+  const int64_t T = x.size(0), K = x.size(1), S = A.size(0), L = A.size(1);
+  check_i32_rows(idx, T, "idx");
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.dim() == 2 &&
+                  t.size(0) == T && t.size(1) == L,
+              "lora_shrink: t must be fp32 [T, L]");
+  TORCH_CHECK(dsa_lora_shrink_supported((int)T, (int)S, (int)L, (int)K),
+              "lora_shrink: L % 8 == 0, L <= 192, K % 8 == 0, at most 65535 rows");
+  check(dsa_lora_shrink(x.data_ptr(), x.stride(0), A.data_ptr(), idx.data_ptr<int>(), t.data_ptr<float>(), (int)T,
+                        (int)S, (int)L, (int)K, stream()),
+        "lora_shrink");
+}
+
+// y [T, N] bf16 += t [T, nsl * R] @ B[idx]^T per column slice, in place; B bf16 [S, N, R]
+void lora_expand(torch::Tensor t, torch::Tensor B, torch::Tensor idx, std::vector<int64_t> slice_ends,
+                 torch::Tensor y) {
+  TORCH_CHECK(y.is_cuda() && y.scalar_type() == torch::kBFloat16 && y.dim() == 2 && y.stride(1) == 1,
+              "lora_expand: y must be bf16 [T, N] with contiguous rows");
+  check_bf16(B, "B");
+  TORCH_CHECK(B.dim() == 3 && B.size(1) == y.size(1), "lora_expand: B must be [S, N, R]");
+  const int64_t T = y.size(0), N = y.size(1), S = B.size(0), R = B.size(2), nsl = (int64_t)slice_ends.size();
+  check_i32_rows(idx, T, "idx");
+  TORCH_CHECK(dsa_lora_expand_supported((int)T, (int)S, (int)nsl, (int)R, (int)N),
+              "lora_expand: R in {8, 16, 32, 64}, 1 to 3 slices, at most 65535 rows");
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 && t.is_contiguous() && t.dim() == 2 &&
+                  t.size(0) == T && t.size(1) == nsl * R,
+              "lora_expand: t must be fp32 [T, slices * R]");
+  int ends[3] = {0, 0, 0};
+  int64_t prev = 0;
+  for (int64_t j = 0; j < nsl; ++j) {
+    TORCH_CHECK(slice_ends[j] > prev && slice_ends[j] <= N, "lora_expand: slice_ends must ascend up to N");
+    prev = slice_ends[j];
+    ends[j] = (int)slice_ends[j];
+  }
+  TORCH_CHECK(prev == N, "lora_expand: the last slice must end at N");
+  check(dsa_lora_expand(t.data_ptr<float>(), B.data_ptr(), idx.data_ptr<int>(), y.data_ptr(), y.stride(0), (int)T,
+                        (int)S, (int)nsl, (int)R, (int)N, ends, stream()),
+        "lora_expand");
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1180,4 +1238,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("apply_penalties", &apply_penalties);
   m.def("penalties_update", &penalties_update);
   m.def("logit_bias_max", &dsa_logit_bias_max);
+  m.def("lora_shrink", &lora_shrink);
+  m.def("lora_expand", &lora_expand);
+  m.def("lora_shrink_supported", &lora_shrink_supported);
+  m.def("lora_expand_supported", &lora_expand_supported);
 }

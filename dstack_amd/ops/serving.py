@@ -3,7 +3,8 @@ sampling.
 
 HIP kernels in ``csrc/paged_attn.hip``, ``csrc/paged_prefill.hip``, ``csrc/sampler.hip`` (top-k /
 top-p / min-p truncation, top-N log-probabilities) and ``csrc/penalties.hip`` (presence / frequency /
-repetition penalties, logit_bias) for ROCm tensors; the PyTorch
+repetition penalties, logit_bias) and ``csrc/lora.hip`` (batched multi-LoRA shrink / expand) for ROCm
+tensors; the PyTorch
 functions here are the CPU path of the engine and the fp32 references the GPU tests compare against.
 
 Cache layout (per layer): ``k_cache [pages, KVH, PAGE, 128]`` token-major and
@@ -511,6 +512,83 @@ def penalties_update(state: torch.Tensor, slot: torch.Tensor, tokens: torch.Tens
         return
     rows = slot >= 0
     state[slot[rows].long(), tokens[rows].long()] += 2
+
+
+# ----------------------------------------------------------------------------------------------
+# Batched multi-LoRA projections: csrc/lora.hip
+# ----------------------------------------------------------------------------------------------
+LORA_RANKS = (8, 16, 32, 64)  # padded ranks the kernels take
+
+
+def lora_shrink(x: torch.Tensor, A: torch.Tensor, idx: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``t[r, j] = sum_k x[r, k] * A[idx[r], j, k]`` in fp32 for the rows with ``idx[r] >= 0`` (int32;
+    -1: the row has no adapter and its row of ``t`` is not written).  ``x`` [T, K] (rows contiguous,
+    any row stride), ``A`` [S, L, K] the stacked adapter weights, ``L = slices * R``.  Returns ``t``
+    [T, L] fp32 (``out`` when given; otherwise zeros outside the written rows).  On ROCm tensors
+    nothing is allocated when ``out`` is passed (hipGraph-capturable)."""
+    T, L = x.shape[0], A.shape[1]
+    if out is None:
+        out = torch.zeros(T, L, dtype=torch.float32, device=x.device)
+    if _ext.use_hip(x):
+        _ext.require().lora_shrink(x, A, idx, out)
+        return out
+    rows = idx >= 0
+    if bool(rows.any()):
+        out[rows] = lora_shrink_ref(x, A, idx)[rows]
+    return out
+
+
+def lora_shrink_ref(x, A, idx) -> torch.Tensor:
+    """Reference of :func:`lora_shrink`: fp32 [T, L], zeros in the rows with ``idx < 0``."""
+    t = torch.zeros(x.shape[0], A.shape[1], dtype=torch.float32, device=x.device)
+    for s in torch.unique(idx[idx >= 0]).tolist():
+        rows = idx == s
+        t[rows] = x[rows].float() @ A[s].float().t()
+    return t
+
+
+def lora_expand(t: torch.Tensor, B: torch.Tensor, idx: torch.Tensor, slice_ends, y: torch.Tensor) -> torch.Tensor:
+    """In place, for the rows with ``idx[r] >= 0`` and every column n of slice j (columns
+    ``slice_ends[j - 1] .. slice_ends[j]``): ``y[r, n] = dtype(float(y[r, n]) + sum_i t[r, j * R + i] *
+    B[idx[r], n, i])`` -- the sum in fp32, one rounding.  ``t`` [T, slices * R] fp32, ``B`` [S, N, R]
+    (``alpha / r`` folded in), ``y`` [T, N].  Rows with ``idx < 0`` are not written.  Returns ``y``."""
+    if _ext.use_hip(y):
+        _ext.require().lora_expand(t, B, idx, [int(e) for e in slice_ends], y)
+        return y
+    rows = idx >= 0
+    if bool(rows.any()):
+        y[rows] = lora_expand_ref(t, B, idx, slice_ends, y)[rows]
+    return y
+
+
+def lora_expand_ref(t, B, idx, slice_ends, y) -> torch.Tensor:
+    """Reference of :func:`lora_expand`: a new tensor like ``y`` (rows with ``idx < 0`` are copies)."""
+    out = y.clone()
+    R = B.shape[2]
+    for s in torch.unique(idx[idx >= 0]).tolist():
+        rows = idx == s
+        acc = y[rows].float()
+        lo = 0
+        for j, hi in enumerate(slice_ends):
+            acc[:, lo:hi] += t[rows][:, j * R : (j + 1) * R].float() @ B[s, lo:hi].float().t()
+            lo = hi
+        out[rows] = acc.to(y.dtype)
+    return out
+
+
+def lora_runs(x: torch.Tensor, A: torch.Tensor, B: torch.Tensor, runs, slice_ends, y: torch.Tensor) -> torch.Tensor:
+    """The prefill form: ``runs`` is a list of ``(slot, first row, end row)`` -- a prompt belongs to
+    one request and hence one adapter -- and each run is two library GEMMs, ``x[run] @ A[slot]^T`` and
+    an ``addmm_`` into each column slice of ``y[run]`` (the per-token kernels would stream ``A`` again
+    for every row)."""
+    R = B.shape[2]
+    for s, a, b in runs:
+        t = x[a:b] @ A[s].t()
+        lo = 0
+        for j, hi in enumerate(slice_ends):
+            y[a:b, lo:hi].addmm_(t[:, j * R : (j + 1) * R], B[s, lo:hi].t())
+            lo = hi
+    return y
 
 
 # ----------------------------------------------------------------------------------------------

@@ -30,6 +30,11 @@ def main(argv=None):
     ap.add_argument("--enable-prefix-caching", action="store_true",
                     help="reuse the cached KV pages of a prompt's prefix (64-token pages, LRU eviction); "
                          "not with tensor parallel")
+    ap.add_argument("--lora-modules", nargs="+", default=[], metavar="NAME=PATH",
+                    help="LoRA adapters (PEFT directories) to serve next to the base model; a request picks one "
+                         "by its `model`; not with --quantization fp8 or tensor parallel")
+    ap.add_argument("--max-lora-rank", type=int, default=64,
+                    help="largest adapter rank accepted (the adapter stacks are padded to 8, 16, 32 or 64)")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
     log = logging.getLogger("dstack_amd.serving")
@@ -38,7 +43,13 @@ def main(argv=None):
     import uvicorn
 
     from dstack_amd.serving.engine import LLMEngine
+    from dstack_amd.serving.lora import parse_lora_modules
     from dstack_amd.serving.server import create_app
+
+    try:
+        lora_modules = parse_lora_modules(args.lora_modules)
+    except ValueError as e:
+        ap.error(str(e))
 
     if torch.cuda.is_available():
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
@@ -46,12 +57,15 @@ def main(argv=None):
     eng = LLMEngine.from_model(args.model, max_model_len=args.max_model_len, seed=args.seed, max_batch=args.max_batch,
                                max_prefill_tokens=args.max_prefill_tokens, use_graphs=not args.no_graphs and None,
                                gpu_memory_utilization=args.gpu_memory_utilization, quantization=args.quantization,
-                               kv_cache_dtype=args.kv_cache_dtype, enable_prefix_caching=args.enable_prefix_caching)
+                               kv_cache_dtype=args.kv_cache_dtype, enable_prefix_caching=args.enable_prefix_caching,
+                               lora_modules=lora_modules or None, max_lora_rank=args.max_lora_rank)
     eng.capture_graphs()
     m = eng.model
-    log.info("model %s: %.1f GB weights, %d KV pages (%d tokens), max_model_len %d, %d graph buckets, ready in %.1fs",
+    log.info("model %s: %.1f GB weights, %d KV pages (%d tokens), max_model_len %d, %d decode graphs, ready in %.1fs",
              args.model, m.weight_bytes() / 1e9, m.num_pages, m.num_pages * 64, m.max_model_len, len(eng._graphs),
              time.time() - t0)
+    if lora_modules:
+        log.info("LoRA adapters: %s (rank padded to %d)", ", ".join(lora_modules), m.lora_rank)
     name = args.served_model_name or os.path.basename(os.path.normpath(args.model))
     uvicorn.run(create_app(eng, name), host=args.host, port=args.port, log_level="info")
 

@@ -23,6 +23,11 @@
 // only when the free list is empty.  Admission takes the hits of the prompt's full pages, always
 // leaving at least one token to compute; the plan's starts[i] = PAGE * hits, and the sequence's
 // first own slot is on a fresh page, so a shared page is never written.
+//
+// A sequence may carry a salt (add(..., salt), default 0): it seeds the sequence's hash chain, is
+// stored on every page the sequence registers and is compared on a hit, so sequences with
+// different salts never share pages even for equal tokens (the engine passes the LoRA adapter
+// slot + 1: the K/V of a prompt depend on the adapter that computed them).
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -53,6 +58,7 @@ struct Seq {
   int chained = 0;           // leading pages that are hits or registered: the next page to register
   uint64_t chain_hash = 0;   // hash of page chained - 1
   bool chain_open = true;    // false once a page of this sequence could not be registered
+  uint64_t salt = 0;         // seeds the hash chain; pages are shared only among equal salts
 };
 
 // per-page state of the prefix cache
@@ -64,6 +70,7 @@ struct PageInfo {
   uint32_t gen = 0;          // bumped by every registration: a stale child never matches its parent
   int32_t parent = -1;
   uint32_t parent_gen = 0;
+  uint64_t salt = 0;         // of the sequence that registered the page
   std::vector<int32_t> ids;  // the page's token ids while registered
   std::list<int32_t>::iterator lru_it;
 };
@@ -91,7 +98,7 @@ class Scheduler {
     if (caching_) info_.resize(num_pages);
   }
 
-  void add(int64_t id, int prompt_len, int max_tokens, const py::object& token_ids) {
+  void add(int64_t id, int prompt_len, int max_tokens, const py::object& token_ids, uint64_t salt) {
     if (seqs_.count(id)) throw std::invalid_argument("scheduler: duplicate sequence id");
     if (prompt_len <= 0) throw std::invalid_argument("scheduler: empty prompt");
     if (prompt_len >= max_model_len_) throw std::invalid_argument("scheduler: prompt longer than max_model_len");
@@ -101,6 +108,8 @@ class Scheduler {
     s.id = id;
     s.num_tokens = prompt_len;
     s.max_tokens = std::min(max_tokens, max_model_len_);
+    s.salt = salt;
+    s.chain_hash = salt;
     if (!token_ids.is_none()) {
       auto arr = py::array_t<int32_t, py::array::c_style | py::array::forcecast>::ensure(token_ids);
       if (!arr || arr.ndim() != 1 || arr.shape(0) != prompt_len)
@@ -338,7 +347,7 @@ class Scheduler {
         }
       }
       s.start = s.chained = 0;
-      s.chain_hash = 0;
+      s.chain_hash = s.salt;
       s.chain_open = true;
     }
     s.pages.clear();
@@ -355,12 +364,12 @@ class Scheduler {
     }
     return h & hash_mask_;
   }
-  // the registered page with this hash whose ids and parent are exactly these, or -1
-  int32_t find_page(uint64_t h, const int32_t* ids, int32_t parent) const {
+  // the registered page with this hash whose ids, parent and salt are exactly these, or -1
+  int32_t find_page(uint64_t h, const int32_t* ids, int32_t parent, uint64_t salt) const {
     auto range = by_hash_.equal_range(h);
     for (auto it = range.first; it != range.second; ++it) {
       const PageInfo& pi = info_[it->second];
-      if (pi.parent != parent || (parent >= 0 && pi.parent_gen != info_[parent].gen)) continue;
+      if (pi.salt != salt || pi.parent != parent || (parent >= 0 && pi.parent_gen != info_[parent].gen)) continue;
       if (std::equal(pi.ids.begin(), pi.ids.end(), ids)) return it->second;
     }
     return -1;
@@ -371,12 +380,12 @@ class Scheduler {
     idle_hits = 0;
     if ((int)s.ids.size() < s.num_tokens) return hits;
     const int cap = (s.num_tokens - 1) / page_size_;
-    uint64_t h = 0;
+    uint64_t h = s.salt;
     int32_t parent = -1;
     for (int j = 0; j < cap; ++j) {
       const int32_t* ids = s.ids.data() + (size_t)j * page_size_;
       h = page_hash(h, ids);
-      const int32_t p = find_page(h, ids, parent);
+      const int32_t p = find_page(h, ids, parent, s.salt);
       if (p < 0) break;
       hits.push_back(p);
       if (info_[p].ref == 0) ++idle_hits;
@@ -395,7 +404,7 @@ class Scheduler {
       s.pages.push_back(p);
     }
     s.chained = (int)hits.size();
-    s.chain_hash = hits.empty() ? 0 : info_[hits.back()].hash;
+    s.chain_hash = hits.empty() ? s.salt : info_[hits.back()].hash;
     s.chain_open = true;
     query_tokens_ += s.num_tokens;
     hit_tokens_ += (int64_t)hits.size() * page_size_;
@@ -411,7 +420,7 @@ class Scheduler {
       const int32_t* ids = s.ids.data() + (size_t)j * page_size_;
       const int32_t parent = j > 0 ? s.pages[j - 1] : -1;
       const uint64_t h = page_hash(s.chain_hash, ids);
-      if (find_page(h, ids, parent) >= 0) {
+      if (find_page(h, ids, parent, s.salt) >= 0) {
         s.chain_open = false;
         break;
       }
@@ -421,6 +430,7 @@ class Scheduler {
       pi.gen += 1;
       pi.parent = parent;
       pi.parent_gen = parent >= 0 ? info_[parent].gen : 0;
+      pi.salt = s.salt;
       pi.ids.assign(ids, ids + page_size_);
       by_hash_.emplace(h, s.pages[j]);
       s.chain_hash = h;
@@ -477,7 +487,7 @@ PYBIND11_MODULE(_sched, m) {
            py::arg("max_batch"), py::arg("max_prefill_tokens"), py::arg("max_model_len"), py::arg("pad_to") = 128,
            py::arg("enable_prefix_caching") = false)
       .def("add", &Scheduler::add, py::arg("seq_id"), py::arg("prompt_len"), py::arg("max_tokens"),
-           py::arg("token_ids") = py::none())
+           py::arg("token_ids") = py::none(), py::arg("salt") = (uint64_t)0)
       .def("append", &Scheduler::append, py::arg("seq_id"), py::arg("token") = -1)
       .def("_test_set_hash_mask", &Scheduler::test_set_hash_mask)
       .def("mark_computed", &Scheduler::mark_computed)

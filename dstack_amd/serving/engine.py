@@ -91,6 +91,8 @@ class Request:
     seed: int = 0
     cached_tokens: int = 0  # prompt tokens taken from the prefix cache at admission
     logit_bias: dict = field(default_factory=dict)  # params.logit_bias, validated: {int token id: float}
+    lora: str | None = None  # the adapter the request asked for (add_request(..., lora=name))
+    lora_slot: int = -1  # its slot in the model's adapter stacks; -1: the base model
 
     @property
     def all_ids(self):
@@ -109,11 +111,22 @@ def _buckets(max_batch: int):
 class LLMEngine:
     def __init__(self, model: ServingLlama, max_batch: int = 256, max_prefill_tokens: int = 16384,
                  num_pages: int | None = None, use_graphs: bool | None = None, gpu_memory_utilization: float = 0.90,
-                 eos_token_ids=(), enable_prefix_caching: bool = False):
+                 eos_token_ids=(), enable_prefix_caching: bool = False, lora_modules: dict | None = None,
+                 max_lora_rank: int = 64):
         from dstack_amd.serving import _native
 
         if enable_prefix_caching and model.tp > 1:
             raise ValueError("prefix caching is not supported with tensor parallel yet")
+        # LoRA adapters ({name: PEFT directory}): every adapter gets its own slot of the model's
+        # stacks, loaded here -- before the KV cache is sized -- and kept for the engine's life
+        self.lora_slots: dict[str, int] = {}
+        if lora_modules:
+            _check_lora(model.quantization, model.tp_group if model.tp > 1 else None)
+            model.enable_lora(len(lora_modules), max_lora_rank)
+            for slot, (name, path) in enumerate(lora_modules.items()):
+                model.load_lora(slot, path)
+                self.lora_slots[name] = slot
+        self.lora_requests = {name: 0 for name in self.lora_slots}  # requests admitted per adapter
         self.prefix_caching = bool(enable_prefix_caching)
         self.model = model
         self.device = model.device
@@ -145,7 +158,10 @@ class LLMEngine:
         # (tensor parallel: eager steps, so every rank issues the same RCCL collectives in order)
         self.use_graphs = (self.device.type == "cuda" and self.tp == 1) if use_graphs is None else use_graphs
         self.buckets = _buckets(max_batch)
-        self._graphs: dict[int, torch.cuda.CUDAGraph] = {}
+        # decode graphs: bucket -> graph of the plain step; with adapters loaded also (bucket, "lora")
+        # -> graph of the step with the LoRA kernels (a step whose rows all run the base model
+        # replays the plain one)
+        self._graphs: dict = {}
         self._alloc_static()
         self.stats = dict(prefill_tokens=0, decode_tokens=0, steps=0, preemptions=0, prefill_s=0.0, decode_s=0.0)
         if self.prefix_caching:
@@ -157,6 +173,8 @@ class LLMEngine:
                    quantization: str | None = None, kv_cache_dtype: str = "auto", **kw):
         if kw.get("enable_prefix_caching") and tp_group is not None:
             raise ValueError("prefix caching is not supported with tensor parallel yet")
+        if kw.get("lora_modules"):
+            _check_lora(quantization, tp_group)  # before any weight is loaded
         spec = load_spec(model)
         device = device or ("cuda" if torch.cuda.is_available() else "cpu")
         m = ServingLlama(spec, device, max_model_len=max_model_len, tp_group=tp_group, quantization=quantization,
@@ -203,6 +221,9 @@ class LLMEngine:
         self._reset_penalty_rows(B)
         self._pen_free = list(range(B - 1, -1, -1))
         self._pen_slots: dict[int, int] = {}  # request id -> slot
+        # LoRA: every row's adapter slot (padding rows and base-model rows: -1)
+        self.s_lora_idx = torch.full((B,), -1, **i32)
+        self._lora_rows_set = 0  # leading rows of s_lora_idx that may hold a slot
         self._ws = {b: sops.DecodeWorkspace(b, self.model.H, self.model.KVH, W, dev) for b in self.buckets}
 
     def _reset_penalty_rows(self, m: int):
@@ -215,9 +236,9 @@ class LLMEngine:
         return sops.apply_penalties(logits, self.p_state, slot, pen[0], pen[1], pen[2], pen[3], self.p_bias_ids,
                                     self.p_bias_vals, self.p_bias_n)
 
-    def _decode_body(self, b: int):
+    def _decode_body(self, b: int, lora: bool = False):
         logits = self.model.decode(self.s_tokens[:b], self.s_pos[:b], self.s_slots[:b], self.s_tables[:b],
-                                   self.s_ctx[:b], ws=self._ws[b])
+                                   self.s_ctx[:b], ws=self._ws[b], **(dict(lora_idx=self.s_lora_idx[:b]) if lora else {}))
         self._apply_penalties(logits, self.s_pen_slot[:b], self.s_pen[:, :b])
         sops.sample_filtered(logits, self.s_temps[:b], self.s_seeds[:b], self.s_steps[:b], self.s_top_k[:b],
                              self.s_top_p[:b], self.s_min_p[:b], self.s_out_tok[:b], self.s_out_lp[:b],
@@ -239,6 +260,9 @@ class LLMEngine:
         self.s_top_n.zero_()
         self._filter_rows_set = 0
         self._reset_penalty_rows(self.max_batch)
+        self.s_lora_idx.fill_(-1)
+        self._lora_rows_set = 0
+        variants = [False, True] if self.lora_slots else [False]
         torch.cuda.synchronize(self.device)
         s = torch.cuda.Stream(self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
@@ -247,20 +271,26 @@ class LLMEngine:
             # 4 rows, the in-tree fp8 GEMM, hipBLASLt) and hipBLASLt may not set up a kernel inside
             # a capture ('operation not permitted when stream is capturing')
             for b in self.buckets:
-                self._decode_body(b)
+                for lora in variants:
+                    self._decode_body(b, lora)
         torch.cuda.current_stream(self.device).wait_stream(s)
         pool = torch.cuda.graph_pool_handle()
         self._graph_logits = {}
         for b in reversed(self.buckets):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool):
-                self._graph_logits[b] = self._decode_body(b)
-            self._graphs[b] = g
+            for lora in variants:
+                key = (b, "lora") if lora else b
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, pool=pool):
+                    self._graph_logits[key] = self._decode_body(b, lora)
+                self._graphs[key] = g
         torch.cuda.synchronize(self.device)
 
     # ------------------------------------------------------------------------------------------
-    def add_request(self, prompt_ids, params: SamplingParams | None = None, on_event=None) -> Request:
+    def add_request(self, prompt_ids, params: SamplingParams | None = None, on_event=None,
+                    lora: str | None = None) -> Request:
         params = params or SamplingParams()
+        if lora is not None and lora not in self.lora_slots:
+            raise ValueError(f"unknown LoRA adapter {lora!r} (loaded: {', '.join(self.lora_slots) or 'none'})")
         if not prompt_ids:
             raise ValueError("empty prompt")
         if len(prompt_ids) >= self.model.max_model_len:
@@ -275,8 +305,11 @@ class LLMEngine:
         logit_bias = check_penalties(params, vocab)
         rid = next(self._ids)
         seed = params.seed if params.seed is not None else (rid * 7919 + 17)
-        req = Request(rid, list(prompt_ids), params, on_event=on_event, seed=int(seed), logit_bias=logit_bias)
+        req = Request(rid, list(prompt_ids), params, on_event=on_event, seed=int(seed), logit_bias=logit_bias,
+                      lora=lora, lora_slot=self.lora_slots[lora] if lora is not None else -1)
         with self._lock:
+            if lora is not None:
+                self.lora_requests[lora] += 1
             self.requests[rid] = req
             self._pending.append(req)
         self._wake.set()
@@ -303,8 +336,9 @@ class LLMEngine:
             if req.finished:
                 continue
             if self.prefix_caching:
+                # (the salt keeps the cached K/V of one adapter from serving another's prompt)
                 self.sched.add(req.id, len(req.prompt_ids), len(req.prompt_ids) + req.params.max_tokens,
-                               np.asarray(req.prompt_ids, dtype=np.int32))
+                               np.asarray(req.prompt_ids, dtype=np.int32), salt=req.lora_slot + 1)
             else:
                 self.sched.add(req.id, len(req.prompt_ids), len(req.prompt_ids) + req.params.max_tokens)
         for rid in aborted:
@@ -338,10 +372,16 @@ class LLMEngine:
             if self.tp > 1:
                 self._bcast_prefill(toks, plan["positions"], plan["slots"], plan["offsets"], plan["lens"])
             dev = self.device
+            extra = dict(starts=plan["starts"], block_tables=plan["block_tables"]) if self.prefix_caching else {}
+            if any(r.lora_slot >= 0 for r in reqs):
+                # every row of a prompt's segment (its padding too, so neighbours of one adapter merge)
+                lora_idx = np.full(plan["rows"], -1, dtype=np.int32)
+                ends = list(plan["offsets"][1:]) + [plan["rows"]]
+                for r, off, end in zip(reqs, plan["offsets"], ends):
+                    lora_idx[off:end] = r.lora_slot
+                extra["lora_idx"] = torch.from_numpy(lora_idx)
             logits = self.model.prefill(torch.from_numpy(toks).to(dev), torch.from_numpy(plan["positions"]).to(dev),
-                                        torch.from_numpy(plan["slots"]).to(dev), plan["offsets"], plan["lens"],
-                                        **(dict(starts=plan["starts"], block_tables=plan["block_tables"])
-                                           if self.prefix_caching else {}))
+                                        torch.from_numpy(plan["slots"]).to(dev), plan["offsets"], plan["lens"], **extra)
             tokens, lps, tops = self._sample(logits, reqs)
             self.stats["prefill_tokens"] += int(sum(plan["lens"]))
             if self.prefix_caching:
@@ -455,6 +495,20 @@ class LLMEngine:
         elif self._pen_rows_set:
             self._reset_penalty_rows(self._pen_rows_set)
 
+    def _stage_lora(self, reqs, b: int) -> bool:
+        """Stage the rows' adapter slots into ``s_lora_idx``, as ``_stage_penalties`` does: steps where
+        no request has an adapter copy nothing.  Returns whether the step needs the LoRA kernels."""
+        if self.lora_slots and any(r.lora_slot >= 0 for r in reqs):
+            m = max(b, self._lora_rows_set)
+            idx = torch.tensor([r.lora_slot for r in reqs] + [-1] * (m - len(reqs)), dtype=torch.int32)
+            self.s_lora_idx[:m].copy_(idx, non_blocking=True)
+            self._lora_rows_set = len(reqs)
+            return True
+        if self._lora_rows_set:
+            self.s_lora_idx[: self._lora_rows_set].fill_(-1)
+            self._lora_rows_set = 0
+        return False
+
     @staticmethod
     def _tops(reqs, ids, lps):
         """The top-N outputs on the host, copied only in steps where some request asked for them."""
@@ -497,16 +551,18 @@ class LLMEngine:
             self.s_steps[:n].copy_(steps, non_blocking=True)
             self._stage_filters(reqs, b)
             self._stage_penalties(reqs, b)
+            lora = self._stage_lora(reqs, b)
             if b > n:
                 self.s_slots[n:b].fill_(-1)
                 self.s_ctx[n:b].zero_()
                 self.s_temps[n:b].zero_()
             if self.tp > 1:
                 self._bcast_decode(b)
-            if self._graphs and b in self._graphs:
-                self._graphs[b].replay()
+            key = (b, "lora") if lora else b
+            if self._graphs and key in self._graphs:
+                self._graphs[key].replay()
             else:
-                self._decode_body(b)
+                self._decode_body(b, lora)
             return (self.s_out_tok[:n].tolist(), self.s_out_lp[:n].tolist(),
                     self._tops(reqs, self.s_top_ids[:n], self.s_top_lps[:n]))
 
@@ -568,10 +624,12 @@ class LLMEngine:
             self._bcast([self._STOP])
 
     # ------------------------------------------------------------------------------------------
-    def generate(self, prompts, params: SamplingParams | list | None = None) -> list[Request]:
-        """Offline batch generation: returns the finished requests in prompt order."""
+    def generate(self, prompts, params: SamplingParams | list | None = None, lora=None) -> list[Request]:
+        """Offline batch generation: returns the finished requests in prompt order.  ``lora``: an
+        adapter name for every prompt, or a list with one name (or None: the base model) per prompt."""
         ps = params if isinstance(params, list) else [params or SamplingParams()] * len(prompts)
-        reqs = [self.add_request(p, sp) for p, sp in zip(prompts, ps)]
+        ls = lora if isinstance(lora, (list, tuple)) else [lora] * len(prompts)
+        reqs = [self.add_request(p, sp, lora=l) for p, sp, l in zip(prompts, ps, ls)]
         while any(not r.finished for r in reqs):
             self.step()
         return reqs
@@ -621,6 +679,16 @@ class LLMEngine:
         return dict(self.stats, running=self.sched.num_running, waiting=self.sched.num_waiting + len(self._pending),
                     kv_pages_free=self.sched.free_pages, kv_pages_total=self.sched.num_pages,
                     kv_usage=1.0 - self.sched.free_pages / max(1, self.sched.num_pages))
+
+
+def _check_lora(quantization, tp_group):
+    """The combinations LoRA adapters are refused with (see ``ServingLlama.enable_lora``)."""
+    if quantization == "fp8":
+        raise ValueError("LoRA adapters are not supported with quantization=\"fp8\": the fp8 projections take e4m3 "
+                         "inputs and hand on unscaled outputs, so an adapter has neither a bf16 input nor a "
+                         "finished output to add to (an fp8 KV cache is fine)")
+    if tp_group is not None:
+        raise ValueError("LoRA adapters are not supported with tensor parallel yet")
 
 
 def _filter_top_k_top_p(logits: torch.Tensor, reqs) -> torch.Tensor:

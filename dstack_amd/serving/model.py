@@ -251,6 +251,8 @@ class ServingLlama:
         self.cos, self.sin = rope_tables(self.max_model_len + sops.PAGE, self.D, cfg.rope_theta, spec.rope_scaling,
                                          self.device)
         self.layers: list[dict] = []
+        self.lora: list[dict] = []  # per layer {projection: (A, B)} adapter stacks (enable_lora)
+        self.lora_slots = 0
         self.k_cache: list[torch.Tensor] = []
         self.v_cache: list[torch.Tensor] = []
         self.num_pages = 0
@@ -477,7 +479,110 @@ class ServingLlama:
         for L in self.layers:
             for t in L.values():
                 n += t.nbytes() if isinstance(t, Fp8Weight) else t.numel() * t.element_size()
+        for L in self.lora:
+            n += sum(t.numel() * t.element_size() for ab in L.values() for t in ab)
         return n
+
+    # ------------------------------------------------------------------------------------------
+    # LoRA adapters (serving/lora.py, ops/csrc/lora.hip)
+    # ------------------------------------------------------------------------------------------
+    LORA_KEYS = ("wqkv", "wo", "wgu", "wdown")
+
+    def enable_lora(self, max_loras: int, max_rank: int = 64):
+        """Allocate ``max_loras`` adapter slots: per layer and per base projection the stacked
+        ``A [S, slices * R, in]`` and ``B [S, out, R]`` (zero: an empty slot adds nothing), ``R`` the
+        padded ``max_rank``.  Call before the KV cache is sized."""
+        from dstack_amd.serving.lora import padded_rank
+
+        if self.quantization == "fp8":
+            raise ValueError("LoRA adapters are not supported with quantization=\"fp8\": the fp8 projections take "
+                             "e4m3 inputs and hand on unscaled outputs, so an adapter has neither a bf16 input "
+                             "nor a finished output to add to")
+        if self.tp > 1:
+            raise ValueError("LoRA adapters are not supported with tensor parallel yet")
+        if max_loras < 1:
+            raise ValueError(f"max_loras must be at least 1, got {max_loras}")
+        if self.k_cache:
+            raise ValueError("enable_lora must run before the KV cache is allocated")
+        R = padded_rank(max_rank)
+        d, hd, f = self.cfg.dim, self.D, self.F
+        self.lora_max_rank, self.lora_rank, self.lora_slots = int(max_rank), R, int(max_loras)
+        # column ranges of the independent LoRAs inside each (fused) projection's output
+        self.lora_slices = {"wqkv": (self.H * hd, (self.H + self.KVH) * hd, self.NH * hd), "wo": (d,),
+                            "wgu": (f, 2 * f), "wdown": (d,)}
+        ins = {"wqkv": d, "wo": self.H * hd, "wgu": d, "wdown": f}
+
+        def zeros(*shape):
+            return torch.zeros(*shape, dtype=self.dtype, device=self.device)
+
+        S = self.lora_slots
+        self.lora = [{k: (zeros(S, len(self.lora_slices[k]) * R, ins[k]), zeros(S, self.lora_slices[k][-1], R))
+                      for k in self.LORA_KEYS} for _ in range(self.cfg.n_layers)]
+        self._lora_t = {}  # (rows, L) -> fp32 workspace of the shrink output (static: hipGraph-safe)
+        return self
+
+    @torch.no_grad()
+    def load_lora(self, slot: int, path: str):
+        """Load the PEFT adapter directory ``path`` into slot ``slot`` (whatever the slot held is
+        replaced; targets the adapter does not have stay zero)."""
+        from dstack_amd.serving.lora import TARGETS, read_adapter
+
+        if not self.lora:
+            raise ValueError("load_lora: call enable_lora first")
+        if not 0 <= slot < self.lora_slots:
+            raise ValueError(f"load_lora: slot {slot} is outside [0, {self.lora_slots})")
+        d, hd, f = self.cfg.dim, self.D, self.F
+        shapes = {"q_proj": (self.H * hd, d), "k_proj": (self.KVH * hd, d), "v_proj": (self.KVH * hd, d),
+                  "o_proj": (d, self.H * hd), "gate_proj": (f, d), "up_proj": (f, d), "down_proj": (d, f)}
+        ad = read_adapter(path, self.cfg.n_layers, shapes, self.lora_max_rank)
+        R = self.lora_rank
+        for L in self.lora:
+            for A, B in L.values():
+                A[slot].zero_()
+                B[slot].zero_()
+        for (layer, target), (a, b) in ad.tensors.items():
+            key, j = TARGETS[target]
+            A, B = self.lora[layer][key]
+            ends = self.lora_slices[key]
+            lo = ends[j - 1] if j else 0
+            A[slot, j * R : j * R + ad.rank].copy_(a.to(self.device, self.dtype))
+            B[slot, lo : ends[j], : ad.rank].copy_((b * ad.scale).to(self.device, self.dtype))
+        return ad
+
+    def _lora_ws(self, rows: int, L: int) -> torch.Tensor:
+        t = self._lora_t.get((rows, L))
+        if t is None:
+            t = self._lora_t[(rows, L)] = torch.zeros(rows, L, dtype=torch.float32, device=self.device)
+        return t
+
+    def _lora_add(self, li: int, key: str, x, y, lora):
+        """Add layer ``li``'s adapters of projection ``key`` to its output ``y`` (in place), from the
+        projection's input ``x``.  ``lora``: an int32 [rows] tensor of adapter slots (-1: none) for the
+        per-token kernels of the decode step, or a list of ``(slot, first row, end row)`` runs for
+        prefill (two library GEMMs per run)."""
+        A, B = self.lora[li][key]
+        ends = self.lora_slices[key]
+        if isinstance(lora, list):
+            return sops.lora_runs(x, A, B, lora, ends, y)
+        if self.hip and not (x.stride(-1) == 1 and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0):
+            x = x.contiguous()
+        t = sops.lora_shrink(x, A, lora, out=self._lora_ws(x.shape[0], A.shape[1]))
+        return sops.lora_expand(t, B, lora, ends, y)
+
+    def _lora_runs(self, lora_idx, rows: int):
+        """``lora_idx`` [rows] as a list of ``(slot, first row, end row)`` runs of one adapter
+        (consecutive prompts of one adapter merge; rows without an adapter are left out)."""
+        idx = torch.as_tensor(lora_idx).to("cpu", torch.int64)
+        if idx.numel() != rows:
+            raise ValueError(f"prefill: lora_idx must hold {rows} entries, got {idx.numel()}")
+        if int(idx.max()) >= self.lora_slots:
+            raise ValueError(f"prefill: lora_idx names slot {int(idx.max())} of {self.lora_slots}")
+        cuts = (torch.nonzero(idx[1:] != idx[:-1]).flatten() + 1).tolist()
+        runs = []
+        for a, b in zip([0] + cuts, cuts + [rows]):
+            if int(idx[a]) >= 0:
+                runs.append((int(idx[a]), a, b))
+        return runs
 
     # ------------------------------------------------------------------------------------------
     # KV cache
@@ -638,9 +743,15 @@ class ServingLlama:
         dist.all_gather(parts, logits.contiguous(), group=self.tp_group)
         return torch.cat(parts, dim=-1)
 
-    def _mlp_and_attn_out(self, L, x, o):
-        """(x + o @ wo^T) -> norm -> SwiGLU MLP; returns (new residual, mlp output)."""
+    def _mlp_and_attn_out(self, L, x, o, li: int = 0, lora=None):
+        """(x + o @ wo^T) -> norm -> SwiGLU MLP; returns (new residual, mlp output).  ``lora`` (see
+        ``_lora_add``): layer ``li``'s adapters are added to the o, gate/up and down products."""
         wo = L["wo"]
+        if lora is not None:  # (bf16 weights on one rank: enable_lora refuses fp8 and tensor parallel)
+            ao = self._lora_add(li, "wo", o, self._mm(o, wo), lora)
+            x, h = self._add_rms(x, ao, L["ffn_norm"])
+            a = self._swiglu(self._lora_add(li, "wgu", h, self._mm(h, L["wgu"]), lora))
+            return x, self._lora_add(li, "wdown", a, self._mm(a, L["wdown"]), lora)
         # one rank: the o / down GEMMs' row-wise scales travel with the raw product into the next
         # fused add + RMSNorm; tensor parallel: applied before the all-reduce of the partial sums
         mode = "raw" if self.tp == 1 else "pass"
@@ -695,7 +806,7 @@ class ServingLlama:
     # ------------------------------------------------------------------------------------------
     @torch.no_grad()
     def prefill(self, tokens: torch.Tensor, positions: torch.Tensor, slots: torch.Tensor, offsets, lens,
-                starts=None, block_tables=None):
+                starts=None, block_tables=None, lora_idx=None):
         """Prompts packed into 128-row-aligned segments of one token buffer (``offsets[i]`` is the
         first row of prompt i, ``lens[i]`` its length; padding rows have slot -1).  Writes every
         prompt token's K/V into the cache and returns the logits of each prompt's last token
@@ -707,9 +818,18 @@ class ServingLlama:
         (``sops.paged_prefill``, one launch per layer, after the layer's cache write); segments with
         ``starts[i] == 0`` keep the flash-attention path over their own rows.  With an fp8 KV cache a
         hit segment therefore reads its own chunk's K/V back in e4m3 (as every decode step does),
-        where the flash path uses the bf16 projections."""
+        where the flash path uses the bf16 projections.
+
+        ``lora_idx`` [rows] (int32, host or device; -1: none): the adapter slot of every row.  A prompt
+        has one adapter, so rows form runs, and each run adds its adapter to the four projections
+        with library GEMMs (``sops.lora_runs``)."""
         H, KVH = self.H, self.KVH
         rows = tokens.numel()
+        lora = None
+        if lora_idx is not None:
+            if not self.lora:
+                raise ValueError("prefill: lora_idx given but no adapter slots (enable_lora)")
+            lora = self._lora_runs(lora_idx, rows) or None
         x = F.embedding(tokens, self.embed)
         delta = None
         bounds = []
@@ -752,6 +872,8 @@ class ServingLlama:
                 r = self._mm_fp8(h, wq, defer="raw")
             else:
                 r = self._mm(h, wq) if isinstance(wq, Fp8Weight) else h @ wq.t()
+                if lora is not None:  # before the bias and the RoPE / cache write
+                    self._lora_add(li, "wqkv", h, r, lora)
             if isinstance(r, RawScaled):
                 qkv = r.raw
                 sops.rope_cache_write(qkv, positions, slots, self.cos, self.sin, self.k_cache[li], self.v_cache[li],
@@ -774,15 +896,21 @@ class ServingLlama:
                 else:
                     q, k, v = seg.view(cnt, n, self.NH, self.D).split([H, KVH, KVH], dim=2)
                     o[off : off + n * cnt] = ref.attention(q, k, v, causal=True).reshape(n * cnt, -1)
-            x, delta = self._mlp_and_attn_out(L, x, o)
+            x, delta = self._mlp_and_attn_out(L, x, o, li, lora)
         last = torch.tensor([int(offsets[i]) + int(lens[i]) - 1 for i in range(len(lens))], device=x.device)
         x, h = self._add_rms(x[last], delta.rows(last) if isinstance(delta, RawScaled) else delta[last], self.norm)
         return self._logits(h)
 
     @torch.no_grad()
-    def decode(self, tokens, positions, slots, block_tables, ctx_lens, ws=None):
+    def decode(self, tokens, positions, slots, block_tables, ctx_lens, ws=None, lora_idx=None):
         """One new token per sequence (all inputs [B] / [B, W] device tensors, static shapes):
-        returns logits [B, vocab].  Rows with ``ctx_lens == 0`` (graph padding) are inert."""
+        returns logits [B, vocab].  Rows with ``ctx_lens == 0`` (graph padding) are inert.
+
+        ``lora_idx`` [B] (int32 device tensor; -1: none): every row's adapter slot.  When given, each
+        of the layer's four projections is followed by the batched LoRA kernels (``sops.lora_shrink``
+        on its input, ``sops.lora_expand`` into its output)."""
+        if lora_idx is not None and not self.lora:
+            raise ValueError("decode: lora_idx given but no adapter slots (enable_lora)")
         H, KVH = self.H, self.KVH
         x = F.embedding(tokens, self.embed)
         delta = None
@@ -792,12 +920,14 @@ class ServingLlama:
             else:
                 x, h = self._add_rms(x, delta, L["attn_norm"], next_w=L["wqkv"])
             qkv = self._mm(h, L["wqkv"])
+            if lora_idx is not None:
+                self._lora_add(li, "wqkv", h, qkv, lora_idx)
             if "bqkv" in L:
                 qkv = qkv + L["bqkv"]
             sops.rope_cache_write(qkv, positions, slots, self.cos, self.sin, self.k_cache[li], self.v_cache[li], H, KVH,
                                   self.k_scale, self.v_scale)
             o = sops.paged_decode(qkv, self.k_cache[li], self.v_cache[li], block_tables, ctx_lens, H, KVH, ws=ws,
                                   k_scale=self.k_scale, v_scale=self.v_scale)
-            x, delta = self._mlp_and_attn_out(L, x, o)
+            x, delta = self._mlp_and_attn_out(L, x, o, li, lora_idx)
         _, h = self._add_rms(x, delta, self.norm)
         return self._logits(h)

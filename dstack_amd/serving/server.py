@@ -59,6 +59,8 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
     tok = tokenizer or load_tokenizer(engine.model.spec.path, engine.model.cfg.vocab_size)
     if not engine.eos_token_ids:
         engine.eos_token_ids = tuple(tok.eos_token_ids)
+    if served_model_name in engine.lora_slots:
+        raise ValueError(f"LoRA adapter {served_model_name!r} has the served model's name")
     def _usage(prompt_tokens: int, completion_tokens: int, reqs) -> dict:
         u = {"prompt_tokens": prompt_tokens, "completion_tokens": completion_tokens,
              "total_tokens": prompt_tokens + completion_tokens}
@@ -81,9 +83,14 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
     app = FastAPI(title="dstack-amd serving", lifespan=lifespan)
 
     def _check_model(name):
-        if name and name != served_model_name:
-            raise HTTPException(404, detail={"message": f"model {name!r} does not exist", "type": "invalid_request_error",
-                                             "code": "model_not_found"})
+        """``(name to echo, adapter or None)`` for a request's ``model``: the base model's name (or
+        none) runs the base model, a loaded LoRA adapter's name runs that adapter."""
+        if not name or name == served_model_name:
+            return served_model_name, None
+        if name in engine.lora_slots:
+            return name, name
+        raise HTTPException(404, detail={"message": f"model {name!r} does not exist", "type": "invalid_request_error",
+                                         "code": "model_not_found"})
 
     def _bad(msg: str):
         return HTTPException(400, detail={"message": msg, "type": "invalid_request_error"})
@@ -136,7 +143,7 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
             raise _bad(str(e)) from e
         return sp
 
-    def _submit(ids, params, stop):
+    def _submit(ids, params, stop, lora=None):
         loop = asyncio.get_running_loop()
         q: asyncio.Queue = asyncio.Queue()
 
@@ -144,7 +151,7 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
             loop.call_soon_threadsafe(q.put_nowait, (token, finished, req.finish_reason))
 
         try:
-            req = engine.add_request(ids, params, on_event=on_event)
+            req = engine.add_request(ids, params, on_event=on_event, lora=lora)
         except ValueError as e:
             raise HTTPException(400, detail={"message": str(e), "type": "invalid_request_error"}) from e
         state["requests"] += 1
@@ -229,13 +236,15 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
 
     @app.get("/v1/models")
     async def models():
-        return {"object": "list", "data": [{"id": served_model_name, "object": "model", "created": int(state["started"]),
-                                             "owned_by": "dstack-amd", "max_model_len": engine.model.max_model_len}]}
+        card = {"object": "model", "created": int(state["started"]), "owned_by": "dstack-amd",
+                "max_model_len": engine.model.max_model_len}
+        return {"object": "list", "data": [dict(card, id=served_model_name)] + [
+            dict(card, id=name, parent=served_model_name) for name in engine.lora_slots]}
 
     @app.post("/v1/completions")
     async def completions(request: Request):
         body = await request.json()
-        _check_model(body.get("model"))
+        model_name, lora = _check_model(body.get("model"))
         prompts = _prompts(body)
         n = int(body.get("n") or 1)
         rid = f"cmpl-{uuid.uuid4().hex[:24]}"
@@ -252,7 +261,7 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
         subs = []
         try:
             for p, params in planned:
-                subs.append((p, _submit(p, params, _stop(body))))
+                subs.append((p, _submit(p, params, _stop(body), lora)))
         except BaseException:
             _abort_all(subs)
             raise
@@ -266,7 +275,7 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
                         async for delta, reason in _drain(req, q, st):
                             ch = {"index": idx, "text": delta, "logprobs": None, "finish_reason": reason}
                             yield "data: " + json.dumps({"id": rid, "object": "text_completion", "created": created,
-                                                         "model": served_model_name, "choices": [ch]}) + "\n\n"
+                                                         "model": model_name, "choices": [ch]}) + "\n\n"
                         usage["prompt_tokens"] += len(p)
                         usage["completion_tokens"] += len(req.output_ids)
                 finally:
@@ -274,7 +283,7 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
                 if (body.get("stream_options") or {}).get("include_usage"):
                     usage = _usage(usage["prompt_tokens"], usage["completion_tokens"], [s[1][0] for s in subs])
                     yield "data: " + json.dumps({"id": rid, "object": "text_completion", "created": created,
-                                                 "model": served_model_name, "choices": [], "usage": usage}) + "\n\n"
+                                                 "model": model_name, "choices": [], "usage": usage}) + "\n\n"
                 yield "data: [DONE]\n\n"
 
             return StreamingResponse(gen(), media_type="text/event-stream")
@@ -301,26 +310,26 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
                 ct += len(req.output_ids)
         finally:
             _abort_all(subs)
-        return {"id": rid, "object": "text_completion", "created": created, "model": served_model_name,
+        return {"id": rid, "object": "text_completion", "created": created, "model": model_name,
                 "choices": choices, "usage": _usage(pt, ct, [s[1][0] for s in subs])}
 
     @app.post("/v1/chat/completions")
     async def chat(request: Request):
         body = await request.json()
-        _check_model(body.get("model"))
+        model_name, lora = _check_model(body.get("model"))
         msgs = body.get("messages")
         if not isinstance(msgs, list) or not msgs:
             raise HTTPException(400, detail={"message": "messages must be a non-empty list", "type": "invalid_request_error"})
         ids = tok.encode(tok.apply_chat_template(msgs, add_generation_prompt=True), add_bos=True)
         params = _params(body, len(ids), engine.model.max_model_len - len(ids), chat=True)
         want_lp = bool(body.get("logprobs"))
-        req, q, st = _submit(ids, params, _stop(body))
+        req, q, st = _submit(ids, params, _stop(body), lora)
         rid = f"chatcmpl-{uuid.uuid4().hex[:24]}"
         created = int(time.time())
 
         if body.get("stream"):
             async def gen():
-                head = {"id": rid, "object": "chat.completion.chunk", "created": created, "model": served_model_name}
+                head = {"id": rid, "object": "chat.completion.chunk", "created": created, "model": model_name}
                 yield "data: " + json.dumps(dict(head, choices=[{"index": 0, "delta": {"role": "assistant", "content": ""},
                                                                 "finish_reason": None}])) + "\n\n"
                 sent = 0  # output positions whose logprob entries went out already
@@ -345,7 +354,7 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
         choice = {"index": 0, "message": {"role": "assistant", "content": text}, "finish_reason": reason}
         if want_lp:
             choice["logprobs"] = {"content": [_chat_logprob(req, i) for i in range(len(st.ids))]}
-        return {"id": rid, "object": "chat.completion", "created": created, "model": served_model_name,
+        return {"id": rid, "object": "chat.completion", "created": created, "model": model_name,
                 "choices": [choice],
                 "usage": _usage(len(ids), len(req.output_ids), [req])}
 
@@ -365,6 +374,11 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
         g("dstack_serving_prompt_tokens_total", "prompt tokens received", state["prompt_tokens"], "counter")
         g("dstack_serving_generation_tokens_total", "tokens generated", state["gen_tokens"], "counter")
         g("dstack_serving_preemptions_total", "sequences preempted (recomputed)", m["preemptions"], "counter")
+        if engine.lora_slots:
+            name = "dstack_serving_lora_requests_total"
+            lines.extend([f"# HELP {name} requests received per LoRA adapter", f"# TYPE {name} counter"])
+            for adapter, n in engine.lora_requests.items():
+                lines.append(f'{name}{{adapter="{adapter}"}} {n}')
         if engine.prefix_caching:
             g("dstack_serving_prefix_cache_hit_tokens_total", "prompt tokens served from the prefix cache",
               m["prefix_hit_tokens"], "counter")
