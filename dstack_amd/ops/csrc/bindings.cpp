@@ -101,6 +101,13 @@ hipError_t dsa_gemm_km_f32(const void*, const void*, void*, float*, int, int, in
                            hipStream_t);
 hipError_t dsa_gemm_nt_swiglu_bwd(const void*, const void*, const void*, void*, void*, int, int, int, long, long,
                                   hipStream_t);
+int dsa_mxfp4_gemm_form(int);
+bool dsa_mxfp4_gemm_supported(int, int, int);
+int dsa_mxfp4_gemm_split(int, int, int);
+hipError_t dsa_mxfp4_gemm(const void*, const float*, const void*, const void*, void*, float*, int, int, int, long, long,
+                          int, hipStream_t);
+hipError_t dsa_mxfp4_quant(const void*, long, void*, void*, int, int, hipStream_t);
+hipError_t dsa_mxfp4_dequant(const void*, const void*, void*, long, int, int, hipStream_t);
 }
 
 namespace {
@@ -713,6 +720,72 @@ torch::Tensor fp8_stream_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor 
   return y;
 }
 
+// ---- MXFP4 weights (csrc/mxfp4.hip) ----
+// canonical (codes [N, K/2] uint8, scales [N, K/32] uint8 E8M0) of a bf16 weight, by the OCP MX v1.0 rule
+std::vector<torch::Tensor> quant_mxfp4(torch::Tensor w) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 && w.dim() == 2 && w.stride(1) == 1,
+              "quant_mxfp4: w must be bf16 [N, K] with contiguous rows");
+  TORCH_CHECK(w.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0, "quant_mxfp4: alignment");
+  const int64_t N = w.size(0), K = w.size(1);
+  TORCH_CHECK(N > 0 && K > 0 && K % 32 == 0, "quant_mxfp4: K % 32 == 0");
+  auto codes = torch::empty({N, K / 2}, w.options().dtype(torch::kUInt8));
+  auto scales = torch::empty({N, K / 32}, w.options().dtype(torch::kUInt8));
+  check(dsa_mxfp4_quant(w.data_ptr(), w.stride(0), codes.data_ptr(), scales.data_ptr(), (int)N, (int)K, stream()),
+        "quant_mxfp4");
+  return {codes, scales};
+}
+
+bool mxfp4_gemm_supported(int64_t M, int64_t N, int64_t K) {
+  return dsa_mxfp4_gemm_supported((int)M, (int)N, (int)K);
+}
+
+void check_mxfp4_stored(const torch::Tensor& wc, const torch::Tensor& wsc, int64_t N, int64_t K, const char* what) {
+  for (auto* t : {&wc, &wsc})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kUInt8 && t->is_contiguous() &&
+                    reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                what, ": stored codes and scales are contiguous, 16-byte aligned uint8 ROCm tensors");
+  const int64_t Kp = (K + 511) / 512 * 512;  // the stored form pads K to whole scale dwords
+  TORCH_CHECK(wc.numel() == N * Kp / 2 && wsc.numel() == N * Kp / 32, what,
+              ": stored codes hold N Kp / 2 bytes, stored scales N Kp / 32 (Kp: K rounded up to 512)");
+}
+
+// y[M][N] = bf16(xs[m] (xq W^T)) for a decode batch of up to 256 rows: xq e4m3 [M][K], W the stored MXFP4
+// weight (ops.serving.mxfp4_shuffle); split-K partials are allocated here, added by a second kernel
+torch::Tensor mxfp4_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor wc, torch::Tensor wsc, int64_t N, int64_t K) {
+  TORCH_CHECK(xq.is_cuda() && xq.element_size() == 1 && xq.dim() == 2 && xq.stride(1) == 1 && xq.size(1) == K,
+              "mxfp4_gemm: xq is 1-byte [M, K] with contiguous rows");
+  TORCH_CHECK(xq.stride(0) % 16 == 0 && reinterpret_cast<uintptr_t>(xq.data_ptr()) % 16 == 0,
+              "mxfp4_gemm: 16-byte aligned activation rows");
+  const int64_t M = xq.size(0);
+  TORCH_CHECK(xs.is_cuda() && xs.scalar_type() == torch::kFloat32 && xs.is_contiguous() && xs.numel() == M,
+              "mxfp4_gemm: xs fp32 [M]");
+  TORCH_CHECK(dsa_mxfp4_gemm_supported((int)M, (int)N, (int)K),
+              "mxfp4_gemm: 1 <= M <= 256, N % 256 == 0, K % 512 == 0");
+  check_mxfp4_stored(wc, wsc, N, K, "mxfp4_gemm");
+  const int S = dsa_mxfp4_gemm_split((int)M, (int)N, (int)K);
+  auto y = torch::empty({M, N}, xq.options().dtype(torch::kBFloat16));
+  torch::Tensor part;
+  if (S > 1) part = torch::empty({S, M, N}, xq.options().dtype(torch::kFloat32));
+  check(dsa_mxfp4_gemm(xq.data_ptr(), xs.data_ptr<float>(), wc.data_ptr(), wsc.data_ptr(), y.data_ptr(),
+                       S > 1 ? part.data_ptr<float>() : nullptr, (int)M, (int)N, (int)K, xq.stride(0), y.stride(0), S,
+                       stream()),
+        "mxfp4_gemm");
+  return y;
+}
+
+// the stored MXFP4 weight as bf16 into out[:N, :K] (exact), a caller-provided scratch
+torch::Tensor mxfp4_dequant(torch::Tensor wc, torch::Tensor wsc, int64_t N, int64_t K, torch::Tensor out) {
+  TORCH_CHECK(N > 0 && N % 16 == 0 && K > 0 && K % 32 == 0, "mxfp4_dequant: N % 16 == 0, K % 32 == 0");
+  check_mxfp4_stored(wc, wsc, N, K, "mxfp4_dequant");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kBFloat16 && out.dim() == 2 && out.stride(1) == 1 &&
+                  out.size(0) == N && out.size(1) == K && out.stride(0) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "mxfp4_dequant: out is bf16 [N, K] with contiguous, 16-byte aligned rows");
+  check(dsa_mxfp4_dequant(wc.data_ptr(), wsc.data_ptr(), out.data_ptr(), out.stride(0), (int)N, (int)K, stream()),
+        "mxfp4_dequant");
+  return out;
+}
+
 // out[M][N] (+)= a[K][M]^T b[K][N]  (csrc/gemm_nt.hip KM form: dW = dY^T X, token-major operands);
 // mode 2 = timing-only
 void gemm_km(torch::Tensor a, torch::Tensor b, torch::Tensor out, int64_t mode) {
@@ -1203,6 +1276,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("ws"), pybind11::arg("rw") = 64, pybind11::arg("split") = 1, pybind11::arg("shuffled") = 0,
         pybind11::arg("depth") = 2);
   m.def("fp8_stream_gemm_supported", &fp8_stream_gemm_supported);
+  m.def("quant_mxfp4", &quant_mxfp4);
+  m.def("mxfp4_gemm", &mxfp4_gemm, pybind11::arg("xq"), pybind11::arg("xs"), pybind11::arg("codes"),
+        pybind11::arg("scales"), pybind11::arg("N"), pybind11::arg("K"));
+  m.def("mxfp4_gemm_supported", &mxfp4_gemm_supported);
+  m.def("mxfp4_gemm_form", [](int64_t M) { return dsa_mxfp4_gemm_form((int)M); },
+        "16-row token blocks of the mxfp4_gemm form that runs M rows (1, 4, 8 or 16)");
+  m.def("mxfp4_gemm_split", [](int64_t M, int64_t N, int64_t K) { return dsa_mxfp4_gemm_split((int)M, (int)N, (int)K); },
+        "K slices mxfp4_gemm runs this shape with (0: unsupported)");
+  m.def("mxfp4_dequant", &mxfp4_dequant, pybind11::arg("codes"), pybind11::arg("scales"), pybind11::arg("N"),
+        pybind11::arg("K"), pybind11::arg("out"));
   m.def("swiglu_quant_fp8_rows", &swiglu_quant_fp8_rows, py::arg("gu"), py::arg("rs") = py::none(),
         py::arg("cs") = py::none());
   m.def("scale_rows_cols_", &scale_rows_cols_);

@@ -82,6 +82,56 @@ def fp8_linear(x: torch.Tensor, q: torch.Tensor, s: torch.Tensor) -> torch.Tenso
     return ((xq.float() * xs[:, None]) @ (q.float() * s[:, None]).t()).to(x.dtype)
 
 
+# ----------------------------------------------------------------------------------------------
+# MXFP4 (OCP Microscaling v1.0): e2m1 elements, one E8M0 scale per block of 32 along K
+# ----------------------------------------------------------------------------------------------
+MXFP4_BLOCK = 32
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # magnitude of code 0..7
+
+
+def quant_mxfp4(w: torch.Tensor):
+    """The canonical MXFP4 form of ``w`` [N, K] (bf16 or fp32, finite, K % 32 == 0): ``codes``
+    [N, K/2] uint8 (element 2j in the low nibble, 2j+1 in the high one; a nibble is the sign bit and
+    the e2m1 magnitude code) and ``scales`` [N, K/32] uint8 E8M0 (2^(byte - 127)).
+
+    Per block of 32: e = floor(log2(amax)) - 2 clamped to [-127, 127] (-127 for an all-zero block),
+    each element x / 2^e rounded to nearest even on the e2m1 grid and saturated at 6, with the
+    input's sign bit (zeros and values that round to zero keep it).  Byte 255 is never produced."""
+    N, K = w.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError(f"quant_mxfp4: K = {K} is not a multiple of {MXFP4_BLOCK}")
+    x = w.float().reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = x.abs().amax(dim=-1)
+    _, ex = torch.frexp(amax)  # amax = m * 2^ex with m in [0.5, 1): floor(log2(amax)) = ex - 1
+    e = torch.where(amax > 0, ex.to(torch.int32) - 3, torch.full_like(ex, -127, dtype=torch.int32)).clamp(-127, 127)
+    a = torch.ldexp(x.abs().double(), -e[..., None]).float()  # exact: a power-of-two scaling
+    code = torch.where(a < 2, torch.round(2 * a),
+                       torch.where(a < 4, 2 + torch.round(a), (4 + torch.round(a / 2)).clamp(max=7)))
+    nib = code.to(torch.uint8) | (torch.signbit(x).to(torch.uint8) << 3)
+    nib = nib.reshape(N, K // 2, 2)
+    codes = nib[..., 0] | (nib[..., 1] << 4)
+    return codes.contiguous(), (e + 127).to(torch.uint8).contiguous()
+
+
+def dequant_mxfp4(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """fp32 [N, K] values of a canonical MXFP4 weight (``quant_mxfp4``)."""
+    N, K2 = codes.shape
+    nib = torch.stack([codes & 15, codes >> 4], dim=-1).reshape(N, 2 * K2).long()
+    lut = torch.tensor(E2M1_VALUES, dtype=torch.float64, device=codes.device)
+    mag = lut[nib & 7]
+    val = torch.where((nib & 8) != 0, -mag, mag).reshape(N, -1, MXFP4_BLOCK)
+    return torch.ldexp(val, (scales.to(torch.int32) - 127)[..., None]).float().reshape(N, 2 * K2)
+
+
+def mxfp4_linear(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """x @ W^T for a canonical MXFP4 weight with x quantized per token to e4m3 first (``quant_fp8_rows``):
+    the fp32 product of the two dequantized operands, rounded to bf16 once -- what the decode kernel
+    (``csrc/mxfp4.hip``) computes.  Returned in x's dtype."""
+    xq, xs = quant_fp8_rows(x)
+    y = (xq.float() * xs[:, None]) @ dequant_mxfp4(codes, scales).t()
+    return y.to(torch.bfloat16).to(x.dtype)
+
+
 def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return F.cross_entropy(logits.float(), target, reduction="mean")
 

@@ -637,3 +637,45 @@ def fp8_rows_shuffle(wq: torch.Tensor) -> torch.Tensor:
     src = torch.arange(8, device=wq.device)[None, :] ^ _f8_swz(r % 16)[:, None]  # [r, c] -> source chunk
     idx = src.view(1, 1, 128, 8, 1).expand(N // 128, K // 128, 128, 8, 16)
     return torch.gather(b, 3, idx).contiguous().view(N, K).view(wq.dtype)
+
+
+def mxfp4_shuffle(codes: torch.Tensor, scales: torch.Tensor):
+    """The stored form of a canonical MXFP4 weight (``ops.reference.quant_mxfp4``: ``codes`` [N, K/2],
+    ``scales`` [N, K/32], uint8) -- the order ``mxfp4_gemm`` (``csrc/mxfp4.hip``) streams it in.  Lane
+    ``r + 16 g`` of a wave holds weight row r of a 16-row block and K elements [32 g, 32 g + 32) of a
+    128-wide K-step (one MX block):
+
+    * codes: per 16-row block and K-step, the 1 KiB of the 64 lanes' 16 bytes in lane order, the
+      steps of a block consecutive over K (the nibble order within a byte is the canonical one);
+    * scales: per 16-row block and group of 4 K-steps, the 256 B of the 64 lanes' dwords in lane
+      order, byte j of a dword the scale of step 4 G + j.
+
+    N % 16 == 0, K % 32 == 0.  K is padded to a multiple of 512 (Kp) with zero codes, so that every
+    K-step and scale dword is whole; returns contiguous (codes [N, Kp/2], scales [N, Kp/32]) (done
+    once, when the weights are loaded; the engine keeps only this form)."""
+    N, K2 = codes.shape
+    K = 2 * K2
+    assert N % 16 == 0 and K % 32 == 0 and tuple(scales.shape) == (N, K // 32), (tuple(codes.shape), tuple(scales.shape))
+    assert codes.dtype == torch.uint8 and scales.dtype == torch.uint8
+    pad = -K % 512
+    if pad:
+        codes = torch.nn.functional.pad(codes, (0, pad // 2))
+        scales = torch.nn.functional.pad(scales, (0, pad // 32), value=127)
+        K, K2 = K + pad, K2 + pad // 2
+    c = codes.reshape(N // 16, 16, K // 128, 4, 16)  # (blk, r, t, g, byte)
+    c = c.permute(0, 2, 3, 1, 4).contiguous().view(N, K2)  # (blk, t, g, r, byte)
+    s = scales.reshape(N // 16, 16, K // 512, 4, 4)  # (blk, r, G, j, g)
+    s = s.permute(0, 2, 4, 1, 3).contiguous().view(N, K // 32)  # (blk, G, g, r, j)
+    return c, s
+
+
+def mxfp4_unshuffle(codes: torch.Tensor, scales: torch.Tensor, K: int | None = None):
+    """Inverse of :func:`mxfp4_shuffle`: the canonical (codes, scales) of a stored weight; ``K``: the
+    weight's K where the stored form is padded."""
+    N, K2 = codes.shape
+    Kp = 2 * K2
+    c = codes.reshape(N // 16, Kp // 128, 4, 16, 16).permute(0, 3, 1, 2, 4).contiguous().view(N, K2)
+    s = scales.reshape(N // 16, Kp // 512, 4, 16, 4).permute(0, 3, 1, 4, 2).contiguous().view(N, Kp // 32)
+    if K is not None and K != Kp:
+        c, s = c[:, : K // 2].contiguous(), s[:, : K // 32].contiguous()
+    return c, s

@@ -175,6 +175,8 @@ class LLMEngine:
             raise ValueError("prefix caching is not supported with tensor parallel yet")
         if kw.get("lora_modules"):
             _check_lora(quantization, tp_group)  # before any weight is loaded
+        if quantization == "mxfp4" and tp_group is not None:
+            raise ValueError("quantization=\"mxfp4\" is not supported with tensor parallel yet")
         spec = load_spec(model)
         device = device or ("cuda" if torch.cuda.is_available() else "cpu")
         m = ServingLlama(spec, device, max_model_len=max_model_len, tp_group=tp_group, quantization=quantization,
@@ -185,6 +187,8 @@ class LLMEngine:
             m.init_random(seed)
         if quantization == "fp8":
             m.quantize_fp8()  # before the KV cache is sized: the freed bf16 bytes become KV pages
+        elif quantization == "mxfp4":
+            m.quantize_mxfp4()
         return cls(m, eos_token_ids=spec.eos_token_ids, **kw)
 
     # ------------------------------------------------------------------------------------------
@@ -687,6 +691,10 @@ def _check_lora(quantization, tp_group):
         raise ValueError("LoRA adapters are not supported with quantization=\"fp8\": the fp8 projections take e4m3 "
                          "inputs and hand on unscaled outputs, so an adapter has neither a bf16 input nor a "
                          "finished output to add to (an fp8 KV cache is fine)")
+    if quantization == "mxfp4":
+        raise ValueError("LoRA adapters are not supported with quantization=\"mxfp4\": the decode GEMM takes e4m3 "
+                         "activations against FP4 weights, and the adapter kernels are written for bf16 "
+                         "projections (an fp8 KV cache is fine)")
     if tp_group is not None:
         raise ValueError("LoRA adapters are not supported with tensor parallel yet")
 

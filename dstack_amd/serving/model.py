@@ -59,6 +59,28 @@ class Fp8Weight:
         return self.q.numel() + self.s.numel() * 4 + (self.qs.numel() if self.qs is not None else 0)
 
 
+class Mxfp4Weight:
+    """A linear weight [N, K] in MXFP4 (e2m1 codes, one E8M0 scale per 32 elements along K), kept
+    only in the order the decode GEMM streams it (``ops.serving.mxfp4_shuffle``): ``codes``
+    [N, Kp/2] and ``scales`` [N, Kp/32] uint8, Kp = K rounded up to 512 (zero codes)."""
+
+    __slots__ = ("codes", "scales", "N", "K")
+
+    def __init__(self, codes: torch.Tensor, scales: torch.Tensor, N: int, K: int):
+        self.codes, self.scales, self.N, self.K = codes, scales, int(N), int(K)
+
+    @property
+    def shape(self):
+        return torch.Size((self.N, self.K))
+
+    def nbytes(self) -> int:
+        return self.codes.numel() + self.scales.numel()
+
+    def canonical(self):
+        """(codes [N, K/2], scales [N, K/32]) in the canonical order (``ops.reference.quant_mxfp4``)."""
+        return sops.mxfp4_unshuffle(self.codes, self.scales, self.K)
+
+
 class Fp8Act:
     """Activations already in e4m3 with per-row scales (``q`` uint8 [M, K], ``s`` fp32 [M]),
     produced by the fused add+RMSNorm->fp8 kernel for the next fp8 GEMM."""
@@ -191,8 +213,10 @@ class ServingLlama:
 
     def __init__(self, spec: ModelSpec, device, dtype=None, max_model_len: int | None = None, tp_group=None,
                  quantization: str | None = None, kv_cache_dtype: str = "auto"):
-        if quantization not in (None, "fp8"):
-            raise ValueError(f"unsupported quantization {quantization!r} (supported: fp8)")
+        if quantization not in (None, "fp8", "mxfp4"):
+            raise ValueError(f"unsupported quantization {quantization!r} (supported: fp8, mxfp4)")
+        if quantization == "mxfp4" and tp_group is not None:
+            raise ValueError("quantization=\"mxfp4\" is not supported with tensor parallel yet")
         if kv_cache_dtype not in ("auto", "fp8"):
             raise ValueError(f"unsupported kv_cache_dtype {kv_cache_dtype!r} (supported: auto, fp8)")
         self.quantization = quantization
@@ -431,6 +455,33 @@ class ServingLlama:
         self._add_stream_copies()
         return self
 
+    @torch.no_grad()
+    def quantize_mxfp4(self):
+        """Convert every layer's projections (``FP8_KEYS``) to MXFP4 by the OCP MX v1.0 rule, layer by
+        layer, freeing each bf16 tensor as it goes; the LM head, embedding and norms stay bf16.  One
+        copy is kept, in the decode GEMM's order.  Also allocates the bf16 scratch the prefill-sized
+        GEMMs dequantize into (the largest projection; a workspace, not counted as weight bytes)."""
+        for L in self.layers:
+            for k in self.FP8_KEYS:
+                w = L[k]
+                if isinstance(w, Mxfp4Weight):
+                    continue
+                N, K = w.shape
+                if K % 32 or N % 16:
+                    raise ValueError(f"quantization=\"mxfp4\": projection {k} [{N}, {K}] needs K % 32 == 0 (one scale "
+                                     f"per 32 elements) and N % 16 == 0")
+                if self.hip:
+                    codes, scales = _ext.require().quant_mxfp4(w if w.is_contiguous() else w.contiguous())
+                else:
+                    codes, scales = ref.quant_mxfp4(w)
+                L[k] = Mxfp4Weight(*sops.mxfp4_shuffle(codes, scales), N, K)
+                del w, codes, scales
+            if self.device.type == "cuda":
+                torch.cuda.empty_cache()
+        big = max(L[k].N * L[k].K for L in self.layers for k in self.FP8_KEYS)
+        self._mx_scratch = torch.empty(big, dtype=torch.bfloat16, device=self.device) if self.hip else None
+        return self
+
     def _add_stream_copies(self, reserve_bytes: int = 32 << 30):
         """The pre-shuffled second copies of the weights the streaming decode GEMM takes
         (``_stream_cfg``), when they fit with ``reserve_bytes`` of HBM left for the KV cache and
@@ -478,7 +529,7 @@ class ServingLlama:
         n = sum(t.numel() * t.element_size() for t in ts)
         for L in self.layers:
             for t in L.values():
-                n += t.nbytes() if isinstance(t, Fp8Weight) else t.numel() * t.element_size()
+                n += t.nbytes() if isinstance(t, (Fp8Weight, Mxfp4Weight)) else t.numel() * t.element_size()
         for L in self.lora:
             n += sum(t.numel() * t.element_size() for ab in L.values() for t in ab)
         return n
@@ -498,6 +549,9 @@ class ServingLlama:
             raise ValueError("LoRA adapters are not supported with quantization=\"fp8\": the fp8 projections take "
                              "e4m3 inputs and hand on unscaled outputs, so an adapter has neither a bf16 input "
                              "nor a finished output to add to")
+        if self.quantization == "mxfp4":
+            raise ValueError("LoRA adapters are not supported with quantization=\"mxfp4\": the adapter kernels are "
+                             "written for bf16 projections")
         if self.tp > 1:
             raise ValueError("LoRA adapters are not supported with tensor parallel yet")
         if max_loras < 1:
@@ -662,6 +716,8 @@ class ServingLlama:
         (``csrc/gemv.hip``: 6.1-6.8 TB/s on the 70B projections vs hipBLASLt's 5.5-6.2, where it
         wins; at 2-4 rows hipBLASLt is faster, profiles/bench_gemv_r2o.log); larger batches and
         prefill use hipBLASLt."""
+        if isinstance(w, Mxfp4Weight):
+            return self._mm_mxfp4(x, w)
         if isinstance(w, Fp8Weight) or isinstance(x, Fp8Act):
             return self._mm_fp8(x, w)
         if self.hip and self.gemv and x.shape[0] == 1:
@@ -669,6 +725,24 @@ class ServingLlama:
             if C.gemv_supported(x.shape[0], x.shape[1]) and x.stride(-1) == 1:
                 return C.gemv(x, w)
         return x @ w.t()
+
+    def _mm_mxfp4(self, x, w: Mxfp4Weight):
+        """``x @ W^T`` for an MXFP4 weight.  Up to 256 rows (a decode batch) of a shape the kernel
+        covers: the activations are quantized per token to e4m3 and multiplied by the block-scaled FP4
+        GEMM (``csrc/mxfp4.hip``) straight from the stored weight.  Otherwise (prefill-sized batches,
+        other shapes): the weight is dequantized exactly into the bf16 scratch and multiplied by the
+        bf16 GEMM -- for a 16k-token prefill step of the 70B a few tens of ms of dequant traffic against
+        about 2 s of GEMM.  CPU: ``ref.mxfp4_linear`` for every row count."""
+        if not self.hip:
+            return ref.mxfp4_linear(x, *w.canonical())
+        C = _ext.require()
+        M = x.shape[0]
+        if M <= 256 and C.mxfp4_gemm_supported(M, w.N, w.K):
+            x = x if x.stride(-1) == 1 and x.stride(0) % 8 == 0 else x.contiguous()
+            xq, xs = C.quant_fp8_rows(x)
+            return C.mxfp4_gemm(xq.view(torch.uint8), xs, w.codes, w.scales, w.N, w.K)
+        wd = C.mxfp4_dequant(w.codes, w.scales, w.N, w.K, self._mx_scratch[: w.N * w.K].view(w.N, w.K))
+        return x @ wd.t()
 
     def _mm_fp8(self, x, w: Fp8Weight, defer: str | None = None):
         """``x @ (q * s)^T``: up to 4 rows on the fp8 HIP GEMV (half the weight bytes of the bf16
@@ -871,7 +945,7 @@ class ServingLlama:
                 # prefill-sized: the GEMM's row-wise scales are applied by the RoPE / cache-write kernel
                 r = self._mm_fp8(h, wq, defer="raw")
             else:
-                r = self._mm(h, wq) if isinstance(wq, Fp8Weight) else h @ wq.t()
+                r = self._mm(h, wq) if isinstance(wq, (Fp8Weight, Mxfp4Weight)) else h @ wq.t()
                 if lora is not None:  # before the bias and the RoPE / cache write
                     self._lora_add(li, "wqkv", h, r, lora)
             if isinstance(r, RawScaled):
