@@ -73,10 +73,6 @@ hipError_t dsa_gemm_nt(const void*, const void*, void*, int, int, int, long, lon
 bool dsa_gemm_nt_rope_supported(int, int, int, int, int);
 bool dsa_gemm_nt_f8_supported(int, int, int);
 void dsa_gemm_nt_set_grid(int);
-bool dsa_gemm_nt_f8_swiglu_supported(int, int, int);
-hipError_t dsa_gemm_nt_f8_swiglu(const void*, const void*, void*, float*, const float*, const float*, int, int, int,
-                                 long, long, hipStream_t);
-hipError_t dsa_quant_fp8_rows_pmax(const void*, long, const float*, int, void*, long, float*, int, int, hipStream_t);
 hipError_t dsa_gemm_nt_f8(const void*, const void*, void*, int, int, int, long, long, long, hipStream_t);
 hipError_t dsa_gemm_nt_rope(const void*, const void*, void*, const float*, const float*, int, int, int, long, long,
                             long, int, int, hipStream_t);
@@ -87,12 +83,12 @@ bool dsa_gemm_nt_swiglu_bwd_supported(int, int, int);
 bool dsa_gemm_km_supported(int, int, int);
 hipError_t dsa_fa_dkdv_trace(const void*, const void*, const float*, const float*, float*, float*, unsigned long long*,
                              int, int, int, int, float, hipStream_t);
-bool dsa_fp8_rows_gemm_supported(int, int, int, int, int);
+bool dsa_fp8_rows_gemm_supported(int, int, int);
 bool dsa_fp8_stream_gemm_supported(int, int, int, int, int);
 hipError_t dsa_fp8_stream_gemm(const void*, const float*, const void*, const float*, void*, float*, int, int, int,
                                long, long, long, int, int, int, int, hipStream_t);
-hipError_t dsa_fp8_rows_gemm(const void*, const float*, const void*, const float*, void*, float*, int*, int, int, int,
-                             long, long, long, int, int, int, hipStream_t);
+hipError_t dsa_fp8_rows_gemm(const void*, const float*, const void*, const float*, void*, int, int, int, long, long,
+                             long, hipStream_t);
 hipError_t dsa_gemm_km(const void*, const void*, void*, int, int, int, long, long, long, int, hipStream_t);
 hipError_t dsa_cu_hog(int, int, int, double, int*, hipStream_t);
 hipError_t dsa_synthetic_tokens(const double*, const int64_t*, const int64_t*, const int64_t*, int64_t*, int64_t*,
@@ -566,37 +562,6 @@ void gemm_nt_f8(torch::Tensor a, torch::Tensor w, torch::Tensor out) {
         "gemm_nt_f8");
 }
 
-bool gemm_nt_f8_swiglu_supported(int64_t M, int64_t F, int64_t K) { return dsa_gemm_nt_f8_swiglu_supported(M, F, K); }
-
-// Serving fp8 gate/up + SwiGLU + per-token e4m3 quantization: x [M][K] e4m3 with row scales xs [M],
-// w [2F][K] e4m3 (gate rows then up rows) with per-output-channel scales ws [2F] ->
-// (q [M][F] e4m3, s [M]) -- what swiglu_quant_fp8_rows(raw, xs, ws) gives for the raw product,
-// with a = silu(g) u (bf16) as the only intermediate in HBM.  Also returns a (diagnostics).
-std::vector<torch::Tensor> gemm_nt_f8_swiglu_quant(torch::Tensor x, torch::Tensor w, torch::Tensor xs,
-                                                   torch::Tensor ws) {
-  for (const auto& t : {x, w}) {
-    TORCH_CHECK(t.is_cuda() && t.dim() == 2 && t.stride(1) == 1 && t.element_size() == 1,
-                "gemm_nt_f8_swiglu_quant: operands must be 2-D row-major e4m3 tensors");
-  }
-  const int64_t M = x.size(0), K = x.size(1), F = w.size(0) / 2;
-  TORCH_CHECK(w.size(1) == K && w.size(0) == 2 * F, "gemm_nt_f8_swiglu_quant: shape mismatch");
-  TORCH_CHECK(xs.scalar_type() == torch::kFloat32 && xs.is_contiguous() && xs.numel() == M &&
-                  ws.scalar_type() == torch::kFloat32 && ws.is_contiguous() && ws.numel() == 2 * F,
-              "gemm_nt_f8_swiglu_quant: fp32 scales xs [M], ws [2F]");
-  TORCH_CHECK(dsa_gemm_nt_f8_swiglu_supported(M, F, K), "gemm_nt_f8_swiglu_quant: M % 256, F % 128, K % 256 must be 0");
-  auto a = torch::empty({M, F}, x.options().dtype(torch::kBFloat16));
-  auto pmax = torch::empty({M, F / 32}, x.options().dtype(torch::kFloat32));
-  auto q = torch::empty({M, F}, x.options().dtype(torch::kUInt8));
-  auto s = torch::empty({M}, x.options().dtype(torch::kFloat32));
-  check(dsa_gemm_nt_f8_swiglu(x.data_ptr(), w.data_ptr(), a.data_ptr(), pmax.data_ptr<float>(), xs.data_ptr<float>(),
-                              ws.data_ptr<float>(), M, F, K, x.stride(0), w.stride(0), stream()),
-        "gemm_nt_f8_swiglu");
-  check(dsa_quant_fp8_rows_pmax(a.data_ptr(), F, pmax.data_ptr<float>(), F / 32, q.data_ptr(), F,
-                                s.data_ptr<float>(), M, F, stream()),
-        "quant_fp8_rows_pmax");
-  return {q, s, a};
-}
-
 bool gemm_nt_rope_supported(int64_t M, int64_t N, int64_t K, int64_t S, int64_t rot_cols) {
   return dsa_gemm_nt_rope_supported(M, N, K, S, rot_cols);
 }
@@ -638,17 +603,13 @@ torch::Tensor gemm_nt_trace(torch::Tensor a, torch::Tensor b, torch::Tensor out)
 
 bool gemm_km_supported(int64_t M, int64_t N, int64_t K) { return dsa_gemm_km_supported(M, N, K); }
 
-bool fp8_rows_gemm_supported(int64_t M, int64_t N, int64_t K, int64_t bm, int64_t S) {
-  return dsa_fp8_rows_gemm_supported((int)M, (int)N, (int)K, (int)bm, (int)S);
+bool fp8_rows_gemm_supported(int64_t M, int64_t N, int64_t K) {
+  return dsa_fp8_rows_gemm_supported((int)M, (int)N, (int)K);
 }
 
 // y[M][N] = bf16(xs[m] ws[n] (xq wq^T)) for a decode batch (M <= 256), e4m3 operands
-// (csrc/fp8_gemm.hip); bm = 64 | 128 batch rows per workgroup; S > 1 splits K, with fp32 slabs
-// `part` (S * 256 * N floats) and tickets `cnt` ((N / 128) * ceil(M / bm) int32, zero; left zero);
-// wimg: wq holds ops.serving.fp8_rows_shuffle(w), the weights as per-tile LDS images
-torch::Tensor fp8_rows_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq, torch::Tensor ws, int64_t bm,
-                            int64_t S, c10::optional<torch::Tensor> part, c10::optional<torch::Tensor> cnt,
-                            bool wimg) {
+// (csrc/fp8_gemm.hip)
+torch::Tensor fp8_rows_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq, torch::Tensor ws) {
   for (auto* t : {&xq, &wq}) {
     TORCH_CHECK(t->is_cuda() && t->element_size() == 1 && t->dim() == 2 && t->stride(1) == 1,
                 "fp8_rows_gemm: 1-byte 2-D operands with contiguous rows");
@@ -657,29 +618,15 @@ torch::Tensor fp8_rows_gemm(torch::Tensor xq, torch::Tensor xs, torch::Tensor wq
   }
   const int64_t M = xq.size(0), K = xq.size(1), N = wq.size(0);
   TORCH_CHECK(wq.size(1) == K, "fp8_rows_gemm: K mismatch");
-  TORCH_CHECK(!wimg || wq.is_contiguous(), "fp8_rows_gemm: an LDS-image weight is one contiguous block");
   TORCH_CHECK(xs.is_cuda() && xs.scalar_type() == torch::kFloat32 && xs.is_contiguous() && xs.numel() == M,
               "fp8_rows_gemm: xs fp32 [M]");
   TORCH_CHECK(ws.is_cuda() && ws.scalar_type() == torch::kFloat32 && ws.is_contiguous() && ws.numel() == N,
               "fp8_rows_gemm: ws fp32 [N]");
-  TORCH_CHECK(dsa_fp8_rows_gemm_supported((int)M, (int)N, (int)K, (int)bm, (int)S),
-              "fp8_rows_gemm: M <= 256, N % 128 == 0, bm 64 | 128, K % (128 S) == 0");
-  float* pp = nullptr;
-  int* cp = nullptr;
-  if (S > 1) {
-    TORCH_CHECK(part.has_value() && cnt.has_value(), "fp8_rows_gemm: split-K needs part and cnt");
-    TORCH_CHECK(part->is_cuda() && part->scalar_type() == torch::kFloat32 && part->numel() >= S * 256 * N,
-                "fp8_rows_gemm: part needs S * 256 * N floats");
-    TORCH_CHECK(cnt->is_cuda() && cnt->scalar_type() == torch::kInt32 &&
-                    cnt->numel() >= (N / 128) * ((M + bm - 1) / bm),
-                "fp8_rows_gemm: cnt needs one int32 per output tile");
-    pp = part->data_ptr<float>();
-    cp = cnt->data_ptr<int>();
-  }
+  TORCH_CHECK(dsa_fp8_rows_gemm_supported((int)M, (int)N, (int)K),
+              "fp8_rows_gemm: M <= 256, N % 128 == 0, K % 128 == 0");
   auto y = torch::empty({M, N}, xq.options().dtype(torch::kBFloat16));
-  check(dsa_fp8_rows_gemm(xq.data_ptr(), xs.data_ptr<float>(), wq.data_ptr(), ws.data_ptr<float>(), y.data_ptr(), pp,
-                          cp, (int)M, (int)N, (int)K, xq.stride(0), wq.stride(0), y.stride(0), (int)bm, (int)S,
-                          (int)wimg, stream()),
+  check(dsa_fp8_rows_gemm(xq.data_ptr(), xs.data_ptr<float>(), wq.data_ptr(), ws.data_ptr<float>(), y.data_ptr(),
+                          (int)M, (int)N, (int)K, xq.stride(0), wq.stride(0), y.stride(0), stream()),
         "fp8_rows_gemm");
   return y;
 }
@@ -1269,8 +1216,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_km_f32", &gemm_km_f32, pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("acc"),
         pybind11::arg("out") = pybind11::none(), pybind11::arg("mode") = 0);
   m.def("fp8_rows_gemm", &fp8_rows_gemm, pybind11::arg("xq"), pybind11::arg("xs"), pybind11::arg("wq"),
-        pybind11::arg("ws"), pybind11::arg("bm") = 64, pybind11::arg("split") = 1, pybind11::arg("part") = pybind11::none(),
-        pybind11::arg("cnt") = pybind11::none(), pybind11::arg("wimg") = false);
+        pybind11::arg("ws"));
   m.def("fp8_rows_gemm_supported", &fp8_rows_gemm_supported);
   m.def("fp8_stream_gemm", &fp8_stream_gemm, pybind11::arg("xq"), pybind11::arg("xs"), pybind11::arg("wq"),
         pybind11::arg("ws"), pybind11::arg("rw") = 64, pybind11::arg("split") = 1, pybind11::arg("shuffled") = 0,
@@ -1295,8 +1241,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_nt_set_grid", [](int64_t mode) { dsa_gemm_nt_set_grid((int)mode); },
         "in-tree GEMM grid form: -1 environment default, 0 one workgroup per tile, 1 persistent");
   m.def("gemm_nt_f8_supported", &gemm_nt_f8_supported);
-  m.def("gemm_nt_f8_swiglu_quant", &gemm_nt_f8_swiglu_quant);
-  m.def("gemm_nt_f8_swiglu_supported", &gemm_nt_f8_swiglu_supported);
   m.def("gemm_nt_rope_supported", &gemm_nt_rope_supported);
   m.def("gemm_nt_swiglu_supported", &gemm_nt_swiglu_supported);
   m.def("gemm_nt_swiglu_bwd", &gemm_nt_swiglu_bwd, pybind11::arg("dy"), pybind11::arg("wdT"), pybind11::arg("gu"),

@@ -5,23 +5,21 @@
 // At M <= 256 the projection streams its weights once and is HBM-bound (512 flops per weight byte
 // against ~770 at the fp8 MFMA rate), so the design is about keeping every CU's weight stream
 // full with few bytes of anything else:
-//  * One workgroup = a 64- or 128-row batch block x 128 weight rows x all of K or a K slice.  The
-//    batch is cut into blocks so a 256-row batch still gives enough workgroups (4 x N/128 at 64
-//    rows: 256 for a d=8192 projection, one per CU) without split-K partials; the 4 (or 2) batch
-//    blocks of one column block are consecutive multiples of 8 in the grid, i.e. on one XCD under
-//    round-robin placement, so the weight rows come from HBM once and from that XCD's L2 after.
-//    What bounds it is the bytes each CU pulls into LDS (~67 GB/s per CU measured, whatever the
-//    ring depth): a 64-row block moves 24 KiB per 16 KiB of weights, so each weight byte crosses
-//    6x at M = 256.  The 128-row blocks halve the X re-reads (4x) and, for long K, split K in two
-//    (fp32 slabs, the last-arriving slice of a tile adds the others: agent-scope release / ticket /
-//    acquire) to keep 256 workgroups.
-//  * 8 waves: wave (wr, wc) owns 32 batch rows and 32 (BM 64) or 64 (BM 128) weight rows;
+//  * One workgroup = a 64-row batch block x 128 weight rows x all of K.  The batch is cut into
+//    blocks so a 256-row batch still gives enough workgroups (4 x N/128: 256 for a d=8192
+//    projection, one per CU) without split-K partials; the 4 batch blocks of one column block are
+//    consecutive multiples of 8 in the grid, i.e. on one XCD under round-robin placement, so the
+//    weight rows come from HBM once and from that XCD's L2 after.  What bounds it is the bytes each
+//    CU pulls into LDS (~67 GB/s per CU measured, whatever the ring depth): a block moves 24 KiB per
+//    16 KiB of weights, so each weight byte crosses 6x at M = 256.  (128-row blocks, split-K and
+//    weights stored as LDS images were measured and removed: docs/reference/performance.md.)
+//  * 8 waves: wave (wr, wc) owns 32 batch rows and 32 weight rows;
 //    v_mfma_scale_f32_16x16x128_f8f6f4 with unit E8M0 scales (the fp8 rate; the unscaled fp8
 //    MFMA runs at the bf16 rate), weights as the A operand so a lane's accumulator holds 4
 //    consecutive output columns of one batch row (8-byte bf16 stores).
 //  * K advances 128 bytes per step; a step's X tile (64 x 128 B) and W tile (128 x 128 B) are
 //    LDS-DMA'd (global_load_lds_dwordx4, inline asm, hand-counted vmcnt) into a 3-slot ring, two
-//    steps ahead (72 / 96 KiB).  128-byte rows with chunk c of row r at slot
+//    steps ahead (72 KiB).  128-byte rows with chunk c of row r at slot
 //    c ^ ((r>>1 & 1) | (r>>3 & 1) << 2): the two ds_read_b128 of a fragment (row r, 32-byte k chunk
 //    g = lane >> 4) hit 16 different 16-byte bank windows in every ds_read_b128 lane group (searched
 //    exhaustively over the XOR-linear swizzles of the row's low 4 bits).
@@ -29,23 +27,23 @@
 
 #include <type_traits>
 
-#include "mfma_tiles.h"
+#include "stream_frag.h"
 
 using namespace dsa;
+using stream::f32x4;
+using stream::i32x4;
+using stream::i32x8;
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int F8_MAXM = 256;           // batch rows
+constexpr int F8_BM = 64;              // batch rows per workgroup
 constexpr int F8_BN = 128;             // weight rows per workgroup
 constexpr int F8_BK = 128;             // K bytes per step
+constexpr int F8_XT = F8_BM * F8_BK;   // 8 KiB X tile
 constexpr int F8_WT = F8_BN * F8_BK;   // 16 KiB W tile
+constexpr int F8_STAGE = F8_XT + F8_WT;
 constexpr int F8_NSTAGE = 3;
-template <int BM>
-constexpr int f8_stage() { return BM * F8_BK + F8_WT; }  // X tile + W tile
 
 struct F8Args {
   const uint8_t* X;
@@ -53,11 +51,8 @@ struct F8Args {
   const uint8_t* W;
   const float* ws;
   bf16_t* Y;
-  float* part;   // [S][256][N] fp32 split-K slabs (S > 1)
-  int* cnt;      // one ticket per output tile, zero between launches (S > 1)
   long ldx, ldw, ldy;
-  int M, N, K, S;
-  int wimg;      // W stored as LDS images (ops.serving.fp8_rows_shuffle): 16 KiB per 128-row tile and K-step
+  int M, N, K;
 };
 __device__ __forceinline__ int f8_swz(int r) { return ((r >> 1) & 1) | (((r >> 3) & 1) << 2); }
 
@@ -75,28 +70,14 @@ __device__ __forceinline__ void f8_dma(const uint8_t* sbase, unsigned voff, unsi
       : "memory");
 }
 
-template <int N>
-__device__ __forceinline__ void f8_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ i32x8 f8_frag(const char* p0, const char* p1) {
-  const i32x4 a = *reinterpret_cast<const i32x4*>(p0);
-  const i32x4 b = *reinterpret_cast<const i32x4*>(p1);
-  return i32x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-
 }  // namespace
 
-// BM = 64: waves (wr 0..1, wc 0..3) own 32 batch rows x 32 weight rows; BM = 128: waves (wr 0..3,
-// wc 0..1) own 32 batch rows x 64 weight rows.  Per stage each wave issues BM/64 X pieces and 2 W
-// pieces of 1 KiB.
-template <int BM>
+// waves (wr 0..1, wc 0..3) own 32 batch rows x 32 weight rows; per stage each wave issues 1 X piece
+// and 2 W pieces of 1 KiB
 __global__ __launch_bounds__(512, 2) void fp8_rows_gemm_kernel(F8Args p) {
-  constexpr int XT = BM * F8_BK, STAGE = f8_stage<BM>();
-  constexpr int WR = BM / 32, WCN = 8 / WR;       // wave grid: WR batch x WCN weight slices
-  constexpr int CB = F8_BN / WCN / 16;            // 16-column blocks per wave (2 or 4)
-  constexpr int XP = BM / 64, NP = XP + 2;        // DMA pieces per wave per stage
+  constexpr int WCN = 4;   // wave grid: 2 batch x WCN weight slices
+  constexpr int CB = 2;    // 16-column blocks per wave
+  constexpr int NP = 3;    // DMA pieces per wave per stage
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = w / WCN, wc = w % WCN;
@@ -114,45 +95,39 @@ __global__ __launch_bounds__(512, 2) void fp8_rows_gemm_kernel(F8Args p) {
     nb = blockIdx.x % nN;
     mb = blockIdx.x / nN;
   }
-  const int n0 = nb * F8_BN, m0 = mb * BM, split = blockIdx.y;
-  const int ks = p.K / p.S, nsteps = ks / F8_BK;
+  const int n0 = nb * F8_BN, m0 = mb * F8_BM;
+  const int nsteps = p.K / F8_BK;
 
-  // --- DMA pieces: X pieces w + 8i (rows 8 piece ..), W pieces 8 XP + w + 8i ------------------
+  // --- DMA pieces: X piece w (rows 8 piece ..), W pieces w and w + 8 -----------------------------
   unsigned voff[NP], ldsoff[NP];
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
-    if (i < XP) {
-      const int piece = w + 8 * i;
-      const int row = 8 * piece + (lane >> 3);
-      const int ch = (lane & 7) ^ f8_swz(row & 15);
+    const int piece = i == 0 ? w : w + 8 * (i - 1);
+    const int row = 8 * piece + (lane >> 3);
+    const int ch = (lane & 7) ^ f8_swz(row & 15);
+    if (i == 0) {
       const int srow = m0 + row < p.M ? m0 + row : p.M - 1;  // padded rows re-read the last real row
       voff[i] = (unsigned)((long)srow * p.ldx + ch * 16);
       ldsoff[i] = (unsigned)(piece * 1024);
     } else {
-      const int piece = w + 8 * (i - XP);
-      const int row = 8 * piece + (lane >> 3);
-      const int ch = (lane & 7) ^ f8_swz(row & 15);
-      // LDS-image weights: the piece's 1 KiB is contiguous, already in the swizzled LDS order
-      voff[i] = p.wimg ? (unsigned)(piece * 1024 + lane * 16) : (unsigned)((long)row * p.ldw + ch * 16);
-      ldsoff[i] = (unsigned)(XT + piece * 1024);
+      voff[i] = (unsigned)((long)row * p.ldw + ch * 16);
+      ldsoff[i] = (unsigned)(F8_XT + piece * 1024);
     }
   }
   const unsigned lds0 = (unsigned)(uintptr_t)LDS3(char, smem);
-  const uint8_t* xbase = p.X + (long)split * ks;
-  const uint8_t* wbase = p.wimg ? p.W + ((long)nb * (p.K / F8_BK) + (long)split * nsteps) * (F8_BN * F8_BK)
-                                : p.W + (long)n0 * p.ldw + (long)split * ks;
-  const long wstep = p.wimg ? F8_BN * F8_BK : F8_BK;
+  const uint8_t* xbase = p.X;
+  const uint8_t* wbase = p.W + (long)n0 * p.ldw;
   auto issue = [&](int step) {
-    const unsigned slot = lds0 + (unsigned)((step % F8_NSTAGE) * STAGE);
-    const long ko = (long)step * F8_BK, kw = (long)step * wstep;
+    const unsigned slot = lds0 + (unsigned)((step % F8_NSTAGE) * F8_STAGE);
+    const long ko = (long)step * F8_BK;
 #pragma unroll
-    for (int i = 0; i < NP; ++i) f8_dma(i < XP ? xbase + ko : wbase + kw, voff[i], slot + ldsoff[i]);
+    for (int i = 0; i < NP; ++i) f8_dma((i == 0 ? xbase : wbase) + ko, voff[i], slot + ldsoff[i]);
   };
 
   // --- fragment read offsets: row (lane & 15) of a 16-row block, k chunk pair g = lane >> 4 ----
   const int r = lane & 15, g = lane >> 4, sw = f8_swz(r);
   const int c0 = ((2 * g) ^ sw) * 16, c1 = ((2 * g + 1) ^ sw) * 16;
-  const int xrow = (32 * wr + r) * F8_BK, wrow = XT + (CB * 16 * wc + r) * F8_BK;
+  const int xrow = (32 * wr + r) * F8_BK, wrow = F8_XT + (CB * 16 * wc + r) * F8_BK;
 
   f32x4 acc[2][CB];
 #pragma unroll
@@ -163,19 +138,16 @@ __global__ __launch_bounds__(512, 2) void fp8_rows_gemm_kernel(F8Args p) {
   issue(0);
   if (nsteps > 1) issue(1);
   for (int t = 0; t < nsteps; ++t) {
-    if (t + 1 < nsteps) f8_vmcnt<NP>(); else f8_vmcnt<0>();  // step t landed (this wave's pieces)
-    // ... and every wave's: a bare s_barrier (__syncthreads() is also a fence, for which the compiler
-    // drained vmcnt to 0 here -- the ring then never had a step in flight across the barrier)
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_barrier" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
+    // step t landed: this wave's pieces (counted wait), then every wave's (barrier)
+    if (t + 1 < nsteps) stream::vmcnt<NP>(); else stream::vmcnt<0>();
+    stream::barrier();
     if (t + 2 < nsteps) issue(t + 2);  // into the slot step t-1 read: every wave is past it
-    const char* st = smem + (t % F8_NSTAGE) * STAGE;
+    const char* st = smem + (t % F8_NSTAGE) * F8_STAGE;
     i32x8 wf[CB], xf[2];
 #pragma unroll
-    for (int j = 0; j < CB; ++j) wf[j] = f8_frag(st + wrow + j * 2048 + c0, st + wrow + j * 2048 + c1);
+    for (int j = 0; j < CB; ++j) wf[j] = stream::frag(st + wrow + j * 2048 + c0, st + wrow + j * 2048 + c1);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) xf[i] = f8_frag(st + xrow + i * 2048 + c0, st + xrow + i * 2048 + c1);
+    for (int i = 0; i < 2; ++i) xf[i] = stream::frag(st + xrow + i * 2048 + c0, st + xrow + i * 2048 + c1);
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -185,41 +157,7 @@ __global__ __launch_bounds__(512, 2) void fp8_rows_gemm_kernel(F8Args p) {
 
   // --- epilogue: lane holds C[n = 4(lane>>4) + e][m = lane & 15] of each 16x16 block ------------
   const int mrow = m0 + 32 * wr + r, ncol = n0 + CB * 16 * wc + 4 * g;
-  if (p.S > 1) {
-    // split-K: store the fp32 slab; the last slice of this output tile (ticket) adds the others
-    float* mine = p.part + (long)split * F8_MAXM * p.N;
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < CB; ++j)
-        *reinterpret_cast<f32x4*>(mine + (long)(mrow + 16 * i) * p.N + ncol + 16 * j) = acc[i][j];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int* ticket = reinterpret_cast<int*>(smem);  // the ring is free: every wave is past the loop
-    if (tid == 0) {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const int t = __hip_atomic_fetch_add(p.cnt + blockIdx.x, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *ticket = t;
-      if (t == p.S - 1) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-    }
-    __syncthreads();
-    if (*ticket != p.S - 1) return;
-    for (int s2 = 0; s2 < p.S; ++s2) {
-      if (s2 == split) continue;
-      const float* other = p.part + (long)s2 * F8_MAXM * p.N;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < CB; ++j)
-          acc[i][j] += *reinterpret_cast<const f32x4*>(other + (long)(mrow + 16 * i) * p.N + ncol + 16 * j);
-    }
-    if (tid == 0) __hip_atomic_store(p.cnt + blockIdx.x, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  float wsc[CB][4];
+  f32x4 wsc[CB];
 #pragma unroll
   for (int j = 0; j < CB; ++j)
 #pragma unroll
@@ -230,48 +168,30 @@ __global__ __launch_bounds__(512, 2) void fp8_rows_gemm_kernel(F8Args p) {
     if (m >= p.M) continue;
     const float xsc = p.xs[m];
 #pragma unroll
-    for (int j = 0; j < CB; ++j) {
-      unsigned short o[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = f2bf(acc[i][j][e] * xsc * wsc[j][e]);
-      *reinterpret_cast<uint2*>(p.Y + (long)m * p.ldy + ncol + 16 * j) =
-          uint2{(unsigned)o[0] | ((unsigned)o[1] << 16), (unsigned)o[2] | ((unsigned)o[3] << 16)};
-    }
+    for (int j = 0; j < CB; ++j)
+      stream::store_bf16x4(p.Y + (long)m * p.ldy + ncol + 16 * j, acc[i][j], xsc, wsc[j]);
   }
 }
 
-extern "C" bool dsa_fp8_rows_gemm_supported(int M, int N, int K, int bm, int S) {
-  return M > 0 && M <= F8_MAXM && N > 0 && N % F8_BN == 0 && (bm == 64 || bm == 128) && S >= 1 && K > 0 &&
-         K % (F8_BK * S) == 0;
+extern "C" bool dsa_fp8_rows_gemm_supported(int M, int N, int K) {
+  return M > 0 && M <= F8_MAXM && N > 0 && N % F8_BN == 0 && K > 0 && K % F8_BK == 0;
 }
 
 // Y[M][N] = bf16(xs[m] ws[n] X W^T); X [M][K] e4m3 (row stride ldx bytes), W [N][K] e4m3 (ldw
-// bytes), Y bf16 (ldy elements).  bm: batch rows per workgroup (64 or 128).  S > 1 splits K over
-// S workgroups per output tile: `part` holds S * 256 * N floats and `cnt` one int per output tile
-// ((N / 128) * ceil(M / bm)), zero on the first call (each call leaves them zero).  wimg: W holds
-// ops.serving.fp8_rows_shuffle(w) (per 128-row tile and K-step the 16 KiB LDS image; ldw ignored).
+// bytes), Y bf16 (ldy elements).
 extern "C" hipError_t dsa_fp8_rows_gemm(const void* X, const float* xs, const void* W, const float* ws, void* Y,
-                                        float* part, int* cnt, int M, int N, int K, long ldx, long ldw, long ldy,
-                                        int bm, int S, int wimg, hipStream_t st) {
-  if (!dsa_fp8_rows_gemm_supported(M, N, K, bm, S) || ldx % 16 || ldw % 16 || ldy % 4 || ldx < K || ldw < K ||
-      ldy < N)
+                                        int M, int N, int K, long ldx, long ldw, long ldy, hipStream_t st) {
+  if (!dsa_fp8_rows_gemm_supported(M, N, K) || ldx % 16 || ldw % 16 || ldy % 4 || ldx < K || ldw < K || ldy < N)
     return hipErrorInvalidValue;
-  if (S > 1 && (!part || !cnt)) return hipErrorInvalidValue;
   if ((long)(F8_BN - 1) * ldw + K > 0xffffffffL || (long)(M - 1) * ldx + K > 0xffffffffL) return hipErrorInvalidValue;
   static bool attr = false;
   if (!attr) {
-    DSA_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fp8_rows_gemm_kernel<64>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, F8_NSTAGE * f8_stage<64>()));
-    DSA_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fp8_rows_gemm_kernel<128>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, F8_NSTAGE * f8_stage<128>()));
+    DSA_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&fp8_rows_gemm_kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, F8_NSTAGE * F8_STAGE));
     attr = true;
   }
-  F8Args a{(const uint8_t*)X, xs, (const uint8_t*)W, ws, (bf16_t*)Y, part, cnt, ldx, ldw, ldy, M, N, K, S, wimg};
-  const dim3 grid((N / F8_BN) * ((M + bm - 1) / bm), S);
-  if (bm == 64)
-    fp8_rows_gemm_kernel<64><<<grid, 512, F8_NSTAGE * f8_stage<64>(), st>>>(a);
-  else
-    fp8_rows_gemm_kernel<128><<<grid, 512, F8_NSTAGE * f8_stage<128>(), st>>>(a);
+  F8Args a{(const uint8_t*)X, xs, (const uint8_t*)W, ws, (bf16_t*)Y, ldx, ldw, ldy, M, N, K};
+  fp8_rows_gemm_kernel<<<(N / F8_BN) * ((M + F8_BM - 1) / F8_BM), 512, F8_NSTAGE * F8_STAGE, st>>>(a);
   return hipGetLastError();
 }
 
@@ -280,20 +200,21 @@ extern "C" hipError_t dsa_fp8_rows_gemm(const void* X, const float* xs, const vo
 // touch LDS.  fp8_rows_gemm above stages both operands through LDS, and each CU pulls 1.5-3x the
 // weight bytes into it; the 256x256 e4m3 tile (gemm_nt_f8) keeps one 64 KiB K-step (activations +
 // weights) in flight per CU and waits ~2 us for each, i.e. ~3.6 TB/s at gate/up.  Here:
-//  * a workgroup = 4 waves (one per SIMD) x 64 weight rows x all 256 token rows x a K slice; the
-//    256 x 64 fp32 accumulators of a wave fill its 256 accumulation registers;
-//  * each wave loads ITS 64 weight rows straight from HBM into VGPRs (nontemporal: read once) as the
-//    MFMA A operands, two K-steps ahead (3 live register sets, 96 VGPRs) -- no LDS, nothing shared;
+//  * a workgroup = 8 waves x 32 weight rows x all 256 token rows x a K slice (the form the engine
+//    runs; 4 waves x 64 rows, whose 256 x 64 fp32 accumulators fill a wave's 256 accumulation
+//    registers, and 7 waves x 32 rows are compiled too);
+//  * each wave loads ITS weight rows straight from HBM into VGPRs (nontemporal: read once) as the
+//    MFMA A operands, two K-steps ahead (3 of 4 register sets live) -- no LDS, nothing shared;
 //  * the activations (256 x 128 B per K-step, L2-resident: every workgroup reads them) are LDS-DMA'd
 //    into a 4-slot ring (128 KiB) two steps ahead, one barrier per step; every wave reads all 16
 //    token blocks of a step from LDS (the f8_swz swizzle: conflict-free fragment reads);
 //  * v_mfma_scale_f32_16x16x128_f8f6f4 (unit E8M0 scales): a lane's accumulator holds 4 consecutive
 //    output columns (weight rows) of one token row, so the epilogue stores 8-byte bf16 pieces;
-//  * S > 1 splits K: fp32 partials [S][M][N] and fp8_stream_reduce_kernel adds them with the scales.
-// In flight per CU: 2 K-steps x 4 waves x 64 rows x 128 B = 64 KiB of weights, against 32 KiB of
+//  * S > 1 splits K: fp32 partials [S][M][N], added with the scales by stream::reduce_kernel.
+// In flight per CU: 2 K-steps x 256 rows x 128 B = 64 KiB of weights, against 32 KiB of
 // weights (+ 32 KiB of activations) for the LDS-staged 256x256 tile -- the Little's-law term that
-// bounds an HBM stream at this grid size.  LDS fragment reads: 4 bytes per weight byte (a 16-row
-// wave, measured first, read 16 and was LDS-bound at 0.8x hipBLASLt).
+// bounds an HBM stream at this grid size.  LDS fragment reads: 8 bytes per weight byte at 32 rows per
+// wave, 4 at 64 (a 16-row wave, measured first, read 16 and was LDS-bound at 0.8x hipBLASLt).
 // ================================================================================================
 namespace {
 constexpr int FS_NX = 4;                   // activation ring slots
@@ -311,23 +232,10 @@ struct FSArgs {
   int shuffled;  // W in ops.serving.fp8_stream_shuffle order: 0 row-major, 1 per 16-row block, 2 per 256 rows
 };
 
-template <int N>
-__device__ __forceinline__ void fs_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// a bare workgroup barrier: __syncthreads() is a release/acquire fence as well, for which the compiler
-// drains vmcnt to 0 before the s_barrier -- every prefetch in flight would be waited for each step
-__device__ __forceinline__ void fs_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 }  // namespace
 
-// (device functions rather than lambdas of the kernel template: a lambda using these builtins made
-// the host pass drop the template's launch stub -- an undefined symbol at load time)
-// (TAG: the calling kernel's prefetch depth -- one specialization per kernel; the host pass rejected a
-// second kernel template calling an already-used specialization, "substitution failure")
+// (device functions, not lambdas, and TAG -- the calling kernel's prefetch depth -- makes one
+// specialization per kernel: the two host-pass failures recorded in stream_frag.h)
 template <int XP, int NWV, int TAG>
 __device__ __forceinline__ void fs_issue_x(__amdgpu_buffer_rsrc_t xrs, const unsigned (&xoff)[XP], char* slot, int so,
                                            int w) {
@@ -443,8 +351,8 @@ __global__ __launch_bounds__(64 * NWV, 1) void fp8_stream_gemm_kernel(FSArgs p) 
   // the accumulators)
   auto step = [&](int t, auto J, auto ISSUE, auto WN) {
     constexpr int j = decltype(J)::value;
-    fs_vmcnt<decltype(WN)::value>();  // this wave's X(t) and W(t) have landed
-    fs_barrier();                      // every wave's X(t); every wave is past step t-1 (its X slot is free)
+    stream::vmcnt<decltype(WN)::value>();  // this wave's X(t) and W(t) have landed
+    stream::barrier();                     // every wave's X(t); every wave is past step t-1 (its X slot is free)
     if constexpr (decltype(ISSUE)::value) {
       issue_x(t + D);
       load_w(t + D, wf[(j + D) % NSET]);  // a set no live step uses (D + 1 of the 4 are live)
@@ -455,10 +363,11 @@ __global__ __launch_bounds__(64 * NWV, 1) void fp8_stream_gemm_kernel(FSArgs p) 
     constexpr int LA = 2;
     i32x8 xf[LA + 1];
 #pragma unroll
-    for (int i = 0; i < LA; ++i) xf[i] = f8_frag(st + i * 2048 + c0, st + i * 2048 + c1);
+    for (int i = 0; i < LA; ++i) xf[i] = stream::frag(st + i * 2048 + c0, st + i * 2048 + c1);
 #pragma unroll
     for (int tb = 0; tb < 16; ++tb) {
-      if (tb + LA < 16) xf[(tb + LA) % (LA + 1)] = f8_frag(st + (tb + LA) * 2048 + c0, st + (tb + LA) * 2048 + c1);
+      if (tb + LA < 16)
+        xf[(tb + LA) % (LA + 1)] = stream::frag(st + (tb + LA) * 2048 + c0, st + (tb + LA) * 2048 + c1);
 #pragma unroll
       for (int f = 0; f < NF; ++f)
         acc[tb][f] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[j][f], xf[tb % (LA + 1)], acc[tb][f], 0, 0, 0,
@@ -517,33 +426,8 @@ __global__ __launch_bounds__(64 * NWV, 1) void fp8_stream_gemm_kernel(FSArgs p) 
     if (m >= p.M) continue;
     const float xsc = p.xs[m];
 #pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      unsigned short o[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = f2bf(acc[tb][f][e] * xsc * wsc[f][e]);
-      *reinterpret_cast<uint2*>(p.Y + (long)m * p.ldy + n0 + 16 * f + 4 * g) =
-          uint2{(unsigned)o[0] | ((unsigned)o[1] << 16), (unsigned)o[2] | ((unsigned)o[3] << 16)};
-    }
-  }
-}
-
-// y[m][n] = bf16(xs[m] ws[n] sum_s part[s][m][n]), 4 columns per thread
-__global__ __launch_bounds__(256) void fp8_stream_reduce_kernel(const float* __restrict__ part,
-                                                                const float* __restrict__ xs,
-                                                                const float* __restrict__ ws, bf16_t* __restrict__ Y,
-                                                                int M, int N, long ldy, int S) {
-  const long n4 = N / 4, total = (long)M * n4;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int m = (int)(i / n4), n = (int)(i % n4) * 4;
-    f32x4 a = *reinterpret_cast<const f32x4*>(part + (long)m * N + n);
-    for (int s2 = 1; s2 < S; ++s2) a += *reinterpret_cast<const f32x4*>(part + ((long)s2 * M + m) * N + n);
-    const float xsc = xs[m];
-    const f32x4 wsv = *reinterpret_cast<const f32x4*>(ws + n);
-    unsigned short o[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = f2bf(a[e] * xsc * wsv[e]);
-    *reinterpret_cast<uint2*>(Y + (long)m * ldy + n) =
-        uint2{(unsigned)o[0] | ((unsigned)o[1] << 16), (unsigned)o[2] | ((unsigned)o[3] << 16)};
+    for (int f = 0; f < NF; ++f)
+      stream::store_bf16x4(p.Y + (long)m * p.ldy + n0 + 16 * f + 4 * g, acc[tb][f], xsc, wsc[f]);
   }
 }
 
@@ -594,10 +478,5 @@ extern "C" hipError_t dsa_fp8_stream_gemm(const void* X, const float* xs, const 
   else
     fp8_stream_gemm_kernel<8, 2, 2><<<dim3(N / 256, S), 512, FS_NX * FS_XT, st>>>(a);
   DSA_CHECK(hipGetLastError());
-  if (S > 1) {
-    const long work = (long)M * (N / 4);
-    const int g = (int)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096);
-    fp8_stream_reduce_kernel<<<g, 256, 0, st>>>(part, xs, ws, (bf16_t*)Y, M, N, ldy, S);
-  }
-  return hipGetLastError();
+  return S > 1 ? stream::reduce<true>(part, xs, ws, Y, M, N, ldy, S, st) : hipSuccess;
 }

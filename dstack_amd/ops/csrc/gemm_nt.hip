@@ -74,12 +74,7 @@ constexpr int NT_LDS = 2 * BUF + 2 * 16384;  // 160 KiB: ring + room for the Swi
 // rows of the second 64 unit rows come from 64 rows further on), so a lane's accumulators n and
 // n + 2 are the rotated pair (d, d + 64) of one row and head.
 enum Epi { EPI_STORE = 0, EPI_ACC = 1, EPI_SWIGLU = 2, EPI_SWIGLU_BWD = 3, EPI_NONE = 4, EPI_SWIGLU_R = 5,
-           EPI_SWIGLU_BWD_R = 6, EPI_STORE32 = 7, EPI_ACC32 = 8, EPI_ACC32_BF16 = 9, EPI_ROPE = 10,
-           EPI_SWIGLU_F8 = 11 };
-// EPI_SWIGLU_F8 (F8 only): the serving engine's fp8 gate/up projection -- the SwiGLU tile map of
-// EPI_SWIGLU over raw e4m3 products, the row-wise scales srow[m] scol[n] applied in the epilogue,
-// a = silu(g) u written as bf16 [M][F] (C2) and each wave's per-row max |a| over its 32 columns as
-// pmax[m][F / 32] for the one-pass row quantizer that follows (no [M][2F] product in HBM).
+           EPI_SWIGLU_BWD_R = 6, EPI_STORE32 = 7, EPI_ACC32 = 8, EPI_ACC32_BF16 = 9, EPI_ROPE = 10 };
 
 struct NTArgs {
   const bf16_t* A;
@@ -93,9 +88,6 @@ struct NTArgs {
   const float* rsin;
   int rS;             // ROPE: sequence length (row % rS = position)
   int rcols;          // ROPE: columns [0, rcols) are rotated (multiple of 128)
-  const float* srow;  // SWIGLU_F8: per-row (token) and per-output-channel scales, partial maxima
-  const float* scol;
-  float* pmax;
   long lda, ldb, ldc;
   long ldc32;
   int M, K;
@@ -785,41 +777,6 @@ __global__ __launch_bounds__(512) void gemm_nt_kernel(NTArgs p) {
           *reinterpret_cast<us8*>(gbase + ro * p.ldc + p.bsplit) = nt_pair8(u4[0], u4[1]);
           *reinterpret_cast<us8*>(abase + ro * p.F) = nt_pair8(o4[0], o4[1]);
         }
-    } else if constexpr (EPI == EPI_SWIGLU_F8) {
-      // acc n / n + 2 = raw g / u of (row, f); the deferred-scale SwiGLU-quant's arithmetic
-      // (swiglu_quant_rows_kernel<SCALED>): bf16(raw) * rs * cs -> bf16, a = bf16(silu(g) u)
-      const int q = lane >> 4;
-      const int f0 = nb0 + 32 * wc;  // this wave's 32 columns of the F outputs
-      bf16_t* abase = p.C2 + (long)(m0 + 64 * wr + er) * p.F + f0 + 16 * (q & 1) + 8 * (q >> 1);
-      f4 cg[2], cu[2];
-#pragma unroll
-      for (int n = 0; n < 2; ++n) {
-        cg[n] = *reinterpret_cast<const f4*>(p.scol + f0 + 16 * n + 4 * q);
-        cu[n] = *reinterpret_cast<const f4*>(p.scol + p.F + f0 + 16 * n + 4 * q);
-      }
-      const int P = p.F / 32;
-#pragma unroll
-      for (int ms = 0; ms < 2; ++ms)
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) {
-          const int row = m0 + 128 * ms + 64 * wr + 16 * mi + er;
-          const float r = p.srow[row];
-          us4 o4[2];
-          float am = 0.f;
-#pragma unroll
-          for (int n = 0; n < 2; ++n)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              const float g = bf2f(f2bf(bf2f(f2bf(acc[ms][mi][n][j])) * r * cg[n][j]));
-              const float u = bf2f(f2bf(bf2f(f2bf(acc[ms][mi][n + 2][j])) * r * cu[n][j]));
-              o4[n][j] = f2bf(silu(g) * u);
-              am = fmaxf(am, fabsf(bf2f(o4[n][j])));
-            }
-          *reinterpret_cast<us8*>(abase + (long)(128 * ms + 16 * mi) * p.F) = nt_pair8(o4[0], o4[1]);
-          am = fmaxf(am, __shfl_xor(am, 16));
-          am = fmaxf(am, __shfl_xor(am, 32));
-          if (q == 0) p.pmax[(long)row * P + f0 / 32] = am;
-        }
     } else if constexpr (EPI == EPI_SWIGLU_BWD_R) {
       // acc = da[t][f] (plain column map); 16-byte pieces of 8 consecutive f: g, u loaded, dg, du
       // stored -- dg = da * u * silu'(g), du = da * silu(g), da rounded to bf16 as the unfused path
@@ -1241,38 +1198,6 @@ extern "C" hipError_t dsa_gemm_nt_f8(const void* A, const void* B, void* C, int 
   a.bsplit = 128;
   a.group = nt_group(M / NT_BM, N / NT_BN);
   return nt_launch<EPI_STORE, false, false, true>(a, (M / NT_BM) * (N / NT_BN), st);
-}
-
-// Serving fp8 gate/up with the SwiGLU in the epilogue: X [M][K] e4m3 (ldx bytes), W [2F][K] e4m3
-// (gate rows, then up rows; ldw bytes), rs [M] / cs [2F] the row-wise scales; writes a [M][F] bf16
-// and pmax [M][F / 32] (per-row partial max |a|, for quant_rows_pmax).
-extern "C" bool dsa_gemm_nt_f8_swiglu_supported(int M, int F, int K) {
-  return M > 0 && F > 0 && M % NT_BM == 0 && F % 128 == 0 && K % (4 * NT_BK) == 0;
-}
-
-extern "C" hipError_t dsa_gemm_nt_f8_swiglu(const void* X, const void* W, void* a_out, float* pmax, const float* rs,
-                                            const float* cs, int M, int F, int K, long ldx, long ldw,
-                                            hipStream_t st) {
-  if (!dsa_gemm_nt_f8_swiglu_supported(M, F, K) || ldx % 16 || ldw % 16 || ldx < K || ldw < K)
-    return hipErrorInvalidValue;
-  if (255L * ldx + K > 0xffffffffL || 255L * ldw + K > 0xffffffffL) return hipErrorInvalidValue;
-  NTArgs a{};
-  a.A = (const bf16_t*)X;
-  a.B = (const bf16_t*)W;
-  a.C2 = (bf16_t*)a_out;
-  a.srow = rs;
-  a.scol = cs;
-  a.pmax = pmax;
-  a.lda = ldx / 2;
-  a.ldb = ldw / 2;
-  a.M = M;
-  a.K = K / 2;
-  a.F = F;
-  a.ntn = F / 128;
-  a.nstride = 128;
-  a.bsplit = F;
-  a.group = nt_group(M / NT_BM, F / 128);
-  return nt_launch<EPI_SWIGLU_F8, false, false, true>(a, (M / NT_BM) * (F / 128), st);
 }
 
 // qkv = A[M][K] B[N][K]^T with RoPE on the columns [0, rot_cols) (head_dim 128, rotate-half, fp32

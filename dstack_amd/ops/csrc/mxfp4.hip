@@ -15,8 +15,8 @@
 //    order.  Every weight load is a contiguous 1 KiB, nontemporal (read once), through a buffer
 //    descriptor sized to the exact byte count (a bad offset reads zeros);
 //  * the activations (L2-resident: every workgroup reads them) are LDS-DMA'd into a 4-slot ring
-//    (swizzled: mx_swz), D = 3 K-steps ahead, one bare barrier per step;
-//  * K is split over gridDim.y with fp32 partials [S][M][N] that mxfp4_reduce_kernel adds in a fixed
+//    (swizzled: mx_swz), D = 3 K-steps ahead, one bare barrier per step (stream_frag.h);
+//  * K is split over gridDim.y with fp32 partials [S][M][N] that stream::reduce_kernel adds in a fixed
 //    order (no atomics: a seeded request stays reproducible).
 // Forms, by 16-row token blocks TB (a 1-row batch must not run 16 blocks of MFMAs):
 //    TB 16 (M <= 256) and TB 8 (M <= 128): 8 waves x 2 fragments -- 128 / 64 accumulator VGPRs;
@@ -30,15 +30,14 @@
 
 #include <type_traits>
 
-#include "mfma_tiles.h"
+#include "stream_frag.h"
 
 using namespace dsa;
+using stream::f32x4;
+using stream::i32x4;
+using stream::i32x8;
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int MX_MAXM = 256;   // token rows
 constexpr int MX_BK = 128;     // K elements (activation bytes) per step
@@ -65,23 +64,6 @@ struct MXArgs {
 // uses bits 1 and 2, and with the row's parity (8 chunks per 256-B bank row) the 16 lanes of a group
 // hit 16 different 16-byte bank windows.
 __device__ __forceinline__ int mx_swz(int r) { return (((r >> 1) & 1) << 1) | (((r >> 3) & 1) << 2); }
-
-template <int N>
-__device__ __forceinline__ void mx_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// a bare workgroup barrier (__syncthreads() is a fence too, for which vmcnt is drained to 0)
-__device__ __forceinline__ void mx_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_barrier" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-__device__ __forceinline__ i32x8 mx_xfrag(const char* p0, const char* p1) {
-  const i32x4 a = *reinterpret_cast<const i32x4*>(p0);
-  const i32x4 b = *reinterpret_cast<const i32x4*>(p1);
-  return i32x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
 
 // XP 1 KiB activation pieces (8 token rows x 128 B) per wave and step; pieces past the last one are
 // the last one again (identical bytes to one slot), so every wave issues the same number of loads
@@ -212,8 +194,8 @@ __global__ __launch_bounds__(64 * NWV, TB >= 8 ? 1 : 2) void mxfp4_gemm_kernel(M
   // WN: the vmcnt that leaves this wave's X(t) landed (everything issued after W(t))
   auto step = [&](int t, auto J, auto ISSUE, auto NEXTSC, auto WN) {
     constexpr int j = decltype(J)::value;
-    mx_vmcnt<decltype(WN)::value>();
-    mx_barrier();  // every wave's X(t); every wave is past step t-1 (its X slot is free)
+    stream::vmcnt<decltype(WN)::value>();
+    stream::barrier();  // every wave's X(t); every wave is past step t-1 (its X slot is free)
     if constexpr (decltype(ISSUE)::value) {
       issue_x(t + D);
       load_w(t + D, wf[(j + D) % NSET]);
@@ -224,7 +206,7 @@ __global__ __launch_bounds__(64 * NWV, TB >= 8 ? 1 : 2) void mxfp4_gemm_kernel(M
     if constexpr (TB <= 2) {
       i32x8 xf[TB];
 #pragma unroll
-      for (int tb = 0; tb < TB; ++tb) xf[tb] = mx_xfrag(st + tb * 2048 + c0, st + tb * 2048 + c1);
+      for (int tb = 0; tb < TB; ++tb) xf[tb] = stream::frag(st + tb * 2048 + c0, st + tb * 2048 + c1);
 #pragma unroll
       for (int tb = 0; tb < TB; ++tb)
 #pragma unroll
@@ -235,11 +217,11 @@ __global__ __launch_bounds__(64 * NWV, TB >= 8 ? 1 : 2) void mxfp4_gemm_kernel(M
       constexpr int LA = 2;
       i32x8 xf[LA + 1];
 #pragma unroll
-      for (int i = 0; i < LA; ++i) xf[i] = mx_xfrag(st + i * 2048 + c0, st + i * 2048 + c1);
+      for (int i = 0; i < LA; ++i) xf[i] = stream::frag(st + i * 2048 + c0, st + i * 2048 + c1);
 #pragma unroll
       for (int tb = 0; tb < TB; ++tb) {
         if (tb + LA < TB)
-          xf[(tb + LA) % (LA + 1)] = mx_xfrag(st + (tb + LA) * 2048 + c0, st + (tb + LA) * 2048 + c1);
+          xf[(tb + LA) % (LA + 1)] = stream::frag(st + (tb + LA) * 2048 + c0, st + (tb + LA) * 2048 + c1);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int f = 0; f < NF; ++f) mx_mfma<j>(acc[tb][f], wf[j][f], xf[tb % (LA + 1)], sc[f], unit);
@@ -298,31 +280,8 @@ __global__ __launch_bounds__(64 * NWV, TB >= 8 ? 1 : 2) void mxfp4_gemm_kernel(M
     if (m >= p.M) continue;
     const float xsc = p.xs[m];
 #pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      unsigned short o[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = f2bf(acc[tb][f][e] * xsc);
-      *reinterpret_cast<uint2*>(p.Y + (long)m * p.ldy + n0 + 16 * f + 4 * g) =
-          uint2{(unsigned)o[0] | ((unsigned)o[1] << 16), (unsigned)o[2] | ((unsigned)o[3] << 16)};
-    }
-  }
-}
-
-// y[m][n] = bf16(xs[m] sum_s part[s][m][n]) in the order s = 0, 1, ..: 4 columns per thread
-__global__ __launch_bounds__(256) void mxfp4_reduce_kernel(const float* __restrict__ part,
-                                                           const float* __restrict__ xs, bf16_t* __restrict__ Y,
-                                                           int M, int N, long ldy, int S) {
-  const long n4 = N / 4, total = (long)M * n4;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int m = (int)(i / n4), n = (int)(i % n4) * 4;
-    f32x4 a = *reinterpret_cast<const f32x4*>(part + (long)m * N + n);
-    for (int s2 = 1; s2 < S; ++s2) a += *reinterpret_cast<const f32x4*>(part + ((long)s2 * M + m) * N + n);
-    const float xsc = xs[m];
-    unsigned short o[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = f2bf(a[e] * xsc);
-    *reinterpret_cast<uint2*>(Y + (long)m * ldy + n) =
-        uint2{(unsigned)o[0] | ((unsigned)o[1] << 16), (unsigned)o[2] | ((unsigned)o[3] << 16)};
+    for (int f = 0; f < NF; ++f)
+      stream::store_bf16x4(p.Y + (long)m * p.ldy + n0 + 16 * f + 4 * g, acc[tb][f], xsc);
   }
 }
 
@@ -374,12 +333,7 @@ extern "C" hipError_t dsa_mxfp4_gemm(const void* X, const float* xs, const void*
     default: mxfp4_gemm_kernel<16, 8, 2><<<grid, 512, MX_NX * 16 * 2048, st>>>(a); break;
   }
   DSA_CHECK(hipGetLastError());
-  if (S > 1) {
-    const long work = (long)M * (N / 4);
-    const int g = (int)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096);
-    mxfp4_reduce_kernel<<<g, 256, 0, st>>>(part, xs, (bf16_t*)Y, M, N, ldy, S);
-  }
-  return hipGetLastError();
+  return S > 1 ? stream::reduce<false>(part, xs, nullptr, Y, M, N, ldy, S, st) : hipSuccess;
 }
 
 // ================================================================================================

@@ -813,32 +813,23 @@ def test_swiglu_mlp_fused_matches_separate_kernels(gpu, monkeypatch, wgrad):
         assert rel < 1e-2, f"{name}: rel err {rel}"
 
 
-@pytest.mark.parametrize("M,N,K,bm,split", [(256, 256, 512, 64, 1), (37, 384, 512, 64, 1), (200, 256, 1024, 128, 2),
-                                             (1, 128, 256, 64, 1), (64, 1024, 384, 64, 1), (256, 512, 1024, 128, 1),
-                                             (130, 256, 2048, 128, 4), (256, 1024, 512, 64, 2)])
-@pytest.mark.parametrize("wimg", [False, True])
-def test_fp8_rows_gemm_matches_fp32(gpu, M, N, K, bm, split, wimg):
-    """Decode-batch fp8 GEMM (csrc/fp8_gemm.hip: scaled 16x16x128 f8f6f4 MFMA over 64/128-row batch
-    blocks, optional split-K with a last-arrival combine; weights row-major or as per-tile LDS images,
-    ops.serving.fp8_rows_shuffle) against the fp32 product of the same e4m3 operands and scales;
-    twice, since the split-K tickets must be left at zero."""
-    from dstack_amd.ops.serving import fp8_rows_shuffle
-
+@pytest.mark.parametrize("M,N,K", [(256, 256, 512), (37, 384, 512), (200, 256, 1024), (1, 128, 256), (64, 1024, 384),
+                                   (256, 512, 1024), (130, 256, 2048), (256, 1024, 512)])
+def test_fp8_rows_gemm_matches_fp32(gpu, M, N, K):
+    """Decode-batch fp8 GEMM (csrc/fp8_gemm.hip: scaled 16x16x128 f8f6f4 MFMA over 64-row batch
+    blocks x 128 weight rows) against the fp32 product of the same e4m3 operands and scales."""
     C = _ext.require()
+    assert C.fp8_rows_gemm_supported(M, N, K)
     torch.manual_seed(M + N + K)
     x = torch.randn(M, K, device=gpu, dtype=torch.bfloat16)
     w = torch.randn(N, K, device=gpu, dtype=torch.bfloat16) * 0.05
     xq, xs = ref.quant_fp8_rows(x)
     wq, ws = ref.quant_fp8_rows(w)
     want = (xq.float() * xs[:, None]) @ (wq.float() * ws[:, None]).t()
-    part = torch.empty(split * 256 * N, device=gpu, dtype=torch.float32)
-    cnt = torch.zeros((N // 128) * ((M + bm - 1) // bm), device=gpu, dtype=torch.int32)
-    wk = fp8_rows_shuffle(wq) if wimg else wq
-    for _ in range(2):
-        y = C.fp8_rows_gemm(xq.view(torch.uint8), xs, wk.view(torch.uint8), ws, bm, split, part, cnt, wimg)
-        err = ((y.float() - want).norm() / want.norm()).item()
-        assert err < 1e-2, err
-    assert int(cnt.abs().sum().item()) == 0
+    y = C.fp8_rows_gemm(xq.view(torch.uint8), xs, wq.view(torch.uint8), ws)
+    assert y.shape == (M, N)
+    err = ((y.float() - want).norm() / want.norm()).item()
+    assert err < 1e-2, err
 
 
 @pytest.mark.parametrize("shuffled", [0, 1, 2])
@@ -871,6 +862,33 @@ def test_fp8_stream_gemm_matches_fp32(gpu, M, N, K, split, rw, shuffled):
         assert y.shape == (M, N)
         err = ((y.float() - want).norm() / want.norm()).item()
         assert err < 1e-2, err
+
+
+@pytest.mark.parametrize("M,N,K,split", [(256, 256, 512, 1), (200, 512, 1024, 1), (129, 256, 8192, 2),
+                                         (256, 256, 7168, 7)])
+def test_fp8_stream_gemm_exact(gpu, M, N, K, split):
+    """bf16(fp64 product x xs x ws) exactly: integer e4m3 operands (K <= 1024: -8..8, every partial
+    sum <= 2^16; longer K: -2..2, <= 2^15) and power-of-two scales 2^-3..2^3, so every summation order
+    is exact in fp32.  Padded rows (M = 200) and split-K (fp32 partials, the shared reduce kernel); the
+    split cases run twice and must repeat bit for bit (no atomics)."""
+    from dstack_amd.ops.serving import fp8_stream_shuffle
+
+    C = _ext.require()
+    assert C.fp8_stream_gemm_supported(M, N, K, 32, split)
+    g = torch.Generator(device=gpu).manual_seed(M + N + K + split)
+    amax = 8 if K <= 1024 else 2
+    x = torch.randint(-amax, amax + 1, (M, K), device=gpu, generator=g).float()
+    w = torch.randint(-amax, amax + 1, (N, K), device=gpu, generator=g).float()
+    xs = torch.ldexp(torch.ones(M, device=gpu), torch.randint(-3, 4, (M,), device=gpu, generator=g)).float()
+    ws = torch.ldexp(torch.ones(N, device=gpu), torch.randint(-3, 4, (N,), device=gpu, generator=g)).float()
+    want = ((x.double() @ w.double().t()) * xs.double()[:, None] * ws.double()[None, :]).to(torch.bfloat16)
+    xq = x.to(torch.float8_e4m3fn).view(torch.uint8)
+    wk = fp8_stream_shuffle(w.to(torch.float8_e4m3fn), 256).view(torch.uint8)
+    y = C.fp8_stream_gemm(xq, xs, wk, ws, 32, split, 2)
+    assert y.shape == (M, N) and y.dtype == torch.bfloat16
+    assert torch.equal(y, want), (y.float() - want.float()).abs().max().item()
+    if split > 1:
+        assert torch.equal(C.fp8_stream_gemm(xq, xs, wk, ws, 32, split, 2), y)
 
 
 def test_attention_head_dim_64_runs_sdpa_with_a_warning(gpu):

@@ -748,49 +748,6 @@ def test_gpu_fp8_stream_gemm_in_the_engine(gpu, monkeypatch):
     assert cos > 0.999, cos
 
 
-@pytest.mark.gpu
-def test_gpu_fp8_swiglu_gemm_matches_deferred_kernels(gpu):
-    """The fp8 gate/up GEMM with the SwiGLU and the row-wise scales in its epilogue plus the
-    one-pass row quantizer (csrc/gemm_nt.hip EPI_SWIGLU_F8, fp8.hip quant_rows_pmax) against
-    hipBLASLt's raw product fed to the deferred-scale SwiGLU-quant kernel; and the fp8 engine's
-    prefill logits with the fused path on and off."""
-    from dstack_amd.ops import _ext
-    from dstack_amd.ops import reference as ref
-
-    C = _ext.require()
-    torch.manual_seed(0)
-    one = torch.ones((), device=gpu)
-    for M, F, K in ((256, 1024, 512), (512, 3584, 8192)):
-        assert C.gemm_nt_f8_swiglu_supported(M, F, K)
-        x = torch.randn(M, K, device=gpu, dtype=torch.bfloat16)
-        w = torch.randn(2 * F, K, device=gpu, dtype=torch.bfloat16) * 0.02
-        xq, xs = C.quant_fp8_rows(x)
-        wq, ws = ref.quant_fp8_rows(w)
-        xs = xs.reshape(-1).contiguous()
-        raw = torch._scaled_mm(xq.view(torch.float8_e4m3fn), wq.t(), scale_a=one, scale_b=one,
-                               out_dtype=torch.bfloat16)
-        q_ref, s_ref = C.swiglu_quant_fp8_rows(raw, xs, ws)
-        q, s, a = C.gemm_nt_f8_swiglu_quant(xq.view(torch.uint8), wq.view(torch.uint8), xs, ws)
-        assert torch.allclose(s, s_ref, rtol=1e-3, atol=0), (s - s_ref).abs().max().item()
-        same = (q.view(torch.uint8) == q_ref.view(torch.uint8)).float().mean().item()
-        assert same > 0.999, same
-        deq, deq_ref = q.view(torch.float8_e4m3fn).float() * s[:, None], q_ref.view(torch.float8_e4m3fn).float() * s_ref[:, None]
-        assert ((deq - deq_ref).norm() / deq_ref.norm()).item() < 1e-2
-        exp = ref.swiglu((raw.float() * xs[:, None] * ws[None, :]).bfloat16().float())
-        assert ((a.float() - exp).norm() / exp.norm()).item() < 1e-2
-    kw = dict(device="cuda", max_model_len=1024, max_batch=8, num_pages=64)
-    q8 = LLMEngine.from_model("llama-tiny", quantization="fp8", **kw)
-    n = 512  # a multiple of 256 rows: the fused gate/up path
-    prompt = torch.arange(1, n + 1, device=gpu)
-    pos = torch.arange(n, dtype=torch.int32, device=gpu)
-    slots = torch.arange(n, dtype=torch.int32, device=gpu)
-    q8.model.fp8_swiglu_gemm = False
-    a = q8.model.prefill(prompt, pos, slots, [0], [n]).float()
-    q8.model.fp8_swiglu_gemm = True
-    b = q8.model.prefill(prompt, pos, slots, [0], [n]).float()
-    assert torch.nn.functional.cosine_similarity(a, b, dim=-1).item() > 0.999
-
-
 # ------------------------------------------------------------------------------------------------
 # fp8 (e4m3) KV cache
 # ------------------------------------------------------------------------------------------------
@@ -1037,21 +994,3 @@ def test_fp8_stream_shuffle_layout_matches_the_kernel_addressing():
                         assert torch.equal(flat[off:off + 16], w[16 * nb + r, k:k + 16])
     f8 = sops.fp8_stream_shuffle(w.view(torch.float8_e4m3fn), 224)
     assert f8.dtype == torch.float8_e4m3fn and torch.equal(f8.view(torch.uint8), sh)
-
-
-def test_fp8_rows_shuffle_layout_is_the_kernels_lds_image():
-    """ops.serving.fp8_rows_shuffle (fp8_rows_gemm(..., wimg=True)): per 128-row tile and K-step the
-    1 KiB DMA piece p holds, at lane * 16, row 8 p + lane // 8's chunk (lane % 8) ^ f8_swz(row % 16) --
-    what the kernel's row-major DMA writes to LDS (csrc/fp8_gemm.hip fp8_rows_gemm_kernel)."""
-    N, K = 256, 384
-    w = torch.randint(0, 256, (N, K), dtype=torch.uint8)
-    img = sops.fp8_rows_shuffle(w).flatten()
-    swz = lambda r: ((r >> 1) & 1) | (((r >> 3) & 1) << 2)  # noqa: E731
-    ks = K // 128
-    for nb in range(N // 128):
-        for t in range(ks):
-            for piece in range(16):
-                for lane in range(0, 64, 5):
-                    row, off = 8 * piece + (lane >> 3), (nb * ks + t) * 16384 + piece * 1024 + lane * 16
-                    ch = (lane & 7) ^ swz(row & 15)
-                    assert torch.equal(img[off:off + 16], w[nb * 128 + row, t * 128 + ch * 16:t * 128 + ch * 16 + 16])

@@ -29,61 +29,8 @@ def timed(fn, iters=20):
     return s.elapsed_time(e) / iters
 
 
-def swiglu_mode(C, rows):
-    """gate/up + SwiGLU + per-token quantization (Llama-3-70B, F = 28672): the fused in-tree path
-    against hipBLASLt's raw product + the deferred-scale SwiGLU-quant kernel, and against the
-    decode path (row-wise scaled hipBLASLt + SwiGLU-quant)."""
-    from dstack_amd.ops import reference as ref
-
-    F, K = int(os.getenv("F", "28672")), 8192
-    one = torch.ones((), device="cuda", dtype=torch.float32)
-    res = {}
-    for M in rows:
-        torch.manual_seed(0)
-        x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
-        xq, xs = C.quant_fp8_rows(x)
-        xs = xs.reshape(-1).contiguous()
-        wq = torch.empty(2 * F, K, device="cuda", dtype=torch.float8_e4m3fn)
-        ws = torch.empty(2 * F, device="cuda")
-        for i in range(0, 2 * F, 8192):  # quantize in slices (the bf16 weight is 0.9 GB)
-            q, s_ = ref.quant_fp8_rows(torch.randn(min(8192, 2 * F - i), K, device="cuda") * 0.02)
-            wq[i:i + q.shape[0]], ws[i:i + q.shape[0]] = q, s_
-        ours = lambda: C.gemm_nt_f8_swiglu_quant(xq.view(torch.uint8), wq.view(torch.uint8), xs, ws)  # noqa: E731
-
-        def deferred():
-            raw = torch._scaled_mm(xq.view(torch.float8_e4m3fn), wq.t(), scale_a=one, scale_b=one,
-                                   out_dtype=torch.bfloat16)
-            return C.swiglu_quant_fp8_rows(raw, xs, ws)
-
-        def rowwise():
-            y = torch._scaled_mm(xq.view(torch.float8_e4m3fn), wq.t(), scale_a=xs.view(-1, 1), scale_b=ws.view(1, -1),
-                                 out_dtype=torch.bfloat16)
-            return C.swiglu_quant_fp8_rows(y)
-
-        q1, s1, _ = ours()
-        q2, s2 = deferred()
-        same = (q1.view(torch.uint8) == q2.view(torch.uint8)).float().mean().item()
-        t = {k: [] for k in ("fused", "deferred", "rowwise")}
-        for _ in range(5):
-            t["fused"].append(timed(ours, 10))
-            t["deferred"].append(timed(deferred, 10))
-            t["rowwise"].append(timed(rowwise, 10))
-        r = {"M": M, "F": F, "K": K, "q_bytes_equal": same}
-        r.update({k + "_us": statistics.median(v) * 1e3 for k, v in t.items()})
-        r["speedup_vs_deferred"] = r["deferred_us"] / r["fused_us"]
-        r["speedup_vs_rowwise"] = r["rowwise_us"] / r["fused_us"]
-        res[f"swiglu_m{M}"] = r
-        print(f"swiglu_m{M}", json.dumps({k: round(v, 4) if isinstance(v, float) else v for k, v in r.items()}),
-              flush=True)
-        del wq, ws, xq
-        torch.cuda.empty_cache()
-    print(json.dumps(res))
-
-
 def main():
     C = _ext.require()
-    if os.getenv("MODE") == "swiglu":
-        return swiglu_mode(C, [int(m) for m in os.getenv("ROWS", "256,16384").split(",")])
     rows = [int(m) for m in os.getenv("ROWS", "256,16384").split(",")]
     only = os.getenv("ONLY")
     one = torch.ones((), device="cuda", dtype=torch.float32)
