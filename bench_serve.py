@@ -66,6 +66,11 @@ def main():
     ap.add_argument("--lora-rank", type=int, default=16, help="rank of the random adapters")
     ap.add_argument("--lora-idle", action="store_true",
                     help="with --num-loras: load the adapters but send every request to the base model")
+    ap.add_argument("--speculative-ngram", type=int, default=0, metavar="K",
+                    help="n-gram speculative decoding with K drafts (dstack_amd.serving --speculative-ngram)")
+    ap.add_argument("--ngram-max", type=int, default=3)
+    ap.add_argument("--ngram-min", type=int, default=1)
+    ap.add_argument("--speculative-max-batch", type=int, default=32)
     args = ap.parse_args()
     if args.lora_idle and not args.num_loras:
         ap.error("--lora-idle needs --num-loras")
@@ -94,7 +99,9 @@ def main():
                                max_prefill_tokens=args.max_prefill_tokens, use_graphs=not args.no_graphs and None,
                                quantization=args.quantization, kv_cache_dtype=args.kv_cache_dtype,
                                enable_prefix_caching=args.enable_prefix_caching, lora_modules=lora_modules,
-                               max_lora_rank=max(args.lora_rank, 8))
+                               max_lora_rank=max(args.lora_rank, 8), speculative_ngram=args.speculative_ngram,
+                               ngram_max=args.ngram_max, ngram_min=args.ngram_min,
+                               speculative_max_batch=args.speculative_max_batch)
     if lora_dir is not None:
         lora_dir.cleanup()  # the adapters are in HBM now
     t_load = time.perf_counter() - t0

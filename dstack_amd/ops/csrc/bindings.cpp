@@ -33,6 +33,9 @@ hipError_t dsa_rope_cache_write(void*, const int*, const int*, const float*, con
                                 int, int, float, float, const float*, const float*, hipStream_t);
 hipError_t dsa_paged_decode(const void*, long, const void*, const void*, const int*, int, const int*, void*, float*,
                             float*, int, int, int, int, int, float, int, float, float, hipStream_t);
+hipError_t dsa_paged_verify(const void*, long, int, const void*, const void*, const int*, int, int, const int*,
+                            const int*, void*, float*, float*, int, int, int, int, int, int, float, int, float, float,
+                            hipStream_t);
 hipError_t dsa_sample(const void*, long, int, int, const float*, const int64_t*, const int*, int*, float*,
                       hipStream_t);
 int dsa_top_logprobs_max();
@@ -936,6 +939,47 @@ void paged_decode(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache,
         "paged_decode");
 }
 
+// Attention of up to T new query tokens per sequence over the paged cache (speculative decoding's
+// verify step; csrc/paged_attn.hip).  q: [R, >= H*128] rows, sequence b owning rows b*T .. b*T + T - 1,
+// B = block_tables.size(0) sequences with B*T <= R; out [R, H*128] bf16: rows j >= q_lens[b] of a
+// sequence and the rows from B*T on are written as zeros.
+void paged_verify(torch::Tensor q, torch::Tensor k_cache, torch::Tensor v_cache, torch::Tensor block_tables,
+                  torch::Tensor ctx_lens, torch::Tensor q_lens, torch::Tensor out, torch::Tensor o_part,
+                  torch::Tensor lse_part, int64_t T, int64_t H, int64_t KVH, int64_t nsplit, int64_t pages_per_split,
+                  double scale, double k_scale, double v_scale) {
+  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16 && q.dim() == 2 && q.stride(1) == 1 &&
+                  q.size(1) >= H * 128 && q.stride(0) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "q must be bf16 [R, >= H*128] with contiguous, 16-byte aligned rows");
+  const bool fp8 = check_cache(k_cache, v_cache, KVH);
+  TORCH_CHECK(KVH > 0 && H % KVH == 0 && H / KVH <= 16, "paged_verify: 1..16 query heads per KV head");
+  TORCH_CHECK(T >= 1 && T <= 8, "paged_verify: T must be in [1, 8]");
+  check_i32(block_tables, "block_tables");
+  check_i32(ctx_lens, "ctx_lens");
+  check_i32(q_lens, "q_lens");
+  check_bf16(out, "out");
+  const int64_t R = q.size(0);
+  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(1) >= 1, "block_tables must be [B, W]");
+  const int64_t B = block_tables.size(0);
+  TORCH_CHECK(B * T <= R && ctx_lens.numel() == B && q_lens.numel() == B, "paged_verify: batch mismatch");
+  TORCH_CHECK(nsplit >= 1 && pages_per_split >= 1 && nsplit * pages_per_split >= block_tables.size(1),
+              "splits do not cover the block table");
+  TORCH_CHECK(out.numel() == R * H * 128, "out must be [R, H*128]");
+  if (nsplit > 1) {
+    TORCH_CHECK(o_part.scalar_type() == torch::kFloat32 && o_part.numel() >= R * H * nsplit * 128 &&
+                    lse_part.scalar_type() == torch::kFloat32 && lse_part.numel() >= R * H * nsplit,
+                "paged_verify: split workspaces too small");
+  }
+  check(dsa_paged_verify(q.data_ptr(), q.stride(0), (int)R, k_cache.data_ptr(), v_cache.data_ptr(),
+                         block_tables.data_ptr<int>(), (int)block_tables.stride(0), (int)block_tables.size(1),
+                         ctx_lens.data_ptr<int>(), q_lens.data_ptr<int>(), out.data_ptr(),
+                         nsplit > 1 ? o_part.data_ptr<float>() : nullptr,
+                         nsplit > 1 ? lse_part.data_ptr<float>() : nullptr, (int)B, (int)T, (int)H, (int)KVH,
+                         (int)nsplit, (int)pages_per_split, (float)scale, fp8 ? 1 : 0, (float)k_scale,
+                         (float)v_scale, stream()),
+        "paged_verify");
+}
+
 // Causal attention of n segments of new tokens over the paged cache (csrc/paged_prefill.hip).
 // qkv: [rows, >= H*128] rows (the fused qkv output, read in place); out [rows, H*128] bf16: only rows
 // seg_offsets[s] + i, i < seg_lens[s], are written.  The query at that row sits at position
@@ -1253,6 +1297,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("sin"), py::arg("k_cache"), py::arg("v_cache"), py::arg("H"), py::arg("KVH"), py::arg("k_scale"),
         py::arg("v_scale"), py::arg("rs") = py::none(), py::arg("cs") = py::none());
   m.def("paged_decode", &paged_decode);
+  m.def("paged_verify", &paged_verify);
   m.def("paged_prefill", &paged_prefill, py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("block_tables"), py::arg("seg_offsets"), py::arg("seg_starts"), py::arg("seg_lens"), py::arg("out"),
         py::arg("H"), py::arg("KVH"), py::arg("scale"), py::arg("k_scale"), py::arg("v_scale"),

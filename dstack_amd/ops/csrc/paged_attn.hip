@@ -269,6 +269,117 @@ __global__ __launch_bounds__(256) void paged_combine_kernel(const float* __restr
 }
 
 // ------------------------------------------------------------------------------------------------
+// Paged verify attention (speculative decoding): up to T new query tokens per sequence over its
+// paged context -- the decode kernel with the query token as a second column index.  Sequence b
+// owns rows b*T .. b*T + T - 1 of q and out; query j < q_lens[b] sits at position
+// ctx_lens[b] - q_lens[b] + j and attends to keys 0 .. that position (its own K/V and the earlier
+// drafts' are in the cache already); rows j >= q_lens[b], and every row from B*T on (the row
+// bucket's padding), are written as zeros.
+//
+//  * the T*G (token, query head) pairs of one KV head are the columns: column = j*G + head, in
+//    ceil(T*G / 16) tiles of 16.  One wave carries NT <= 3 tiles (the walk's accumulators, scores
+//    and operands take 72 registers a tile beside the 128 of the K/V fragments in flight; 4 tiles
+//    spill, as in paged_prefill.hip), so every K and V fragment it loads feeds NT MFMAs and the pages
+//    of a KV head are read once for all of them.  More than 3 tiles: `ngroups` such waves, as
+//    workgroups B*KVH apart in the grid -- on the same XCD whenever B*KVH % 8 == 0, so the second
+//    one reads the pages from that XCD's L2;
+//  * keep(c, key) = key < limit[c], the per-column causal limit; the wave walks only up to the page
+//    of its largest limit;
+//  * split-KV as in the decode kernel: grid (ngroups * B * KVH, nsplit), the same fp32 partials and
+//    lse per (row, head, split), merged by paged_combine_kernel over rows * H.  A column with no key
+//    in this split (its limit lies below the split's first page, or its row is past q_lens) is
+//    DEAD: it walks with a zero query and no limit, which keeps its running max finite (the walk
+//    needs a kept key in a column's first page), and nothing of it is kept -- it writes a -inf lse
+//    and no partial (or, unsplit, zeros).  Columns are lane-local in S^T and O^T, so a dead column
+//    cannot touch a live one.
+// The grid is a function of (rows, T, W) only: the step captures into a hipGraph.
+// ------------------------------------------------------------------------------------------------
+template <int NT, bool DIRECT, bool FP8>
+__global__ __launch_bounds__(64) void paged_verify_kernel(
+    const bf16_t* __restrict__ q, long q_stride, int rows, const void* __restrict__ k_cache,
+    const void* __restrict__ v_cache, const int* __restrict__ block_tables, int bt_stride, int bt_width,
+    const int* __restrict__ ctx_lens, const int* __restrict__ q_lens, bf16_t* __restrict__ out,
+    float* __restrict__ o_part, float* __restrict__ lse_part, int B, int Bp, int T, int H, int KVH, int G,
+    int nsplit, int pages_per_split, float scale_log2, float v_scale) {
+  const int bk = blockIdx.x % (Bp * KVH), grp = blockIdx.x / (Bp * KVH);
+  const int kvh = bk % KVH, b = bk / KVH, split = blockIdx.y;
+  const int lane = threadIdx.x, qc = lane & 15, g = lane >> 4;
+  const int ctx = b < B ? ctx_lens[b] : 0;
+  const int ql = b < B ? max(0, min(q_lens[b], min(T, ctx))) : 0;
+  const int first = ctx - ql;  // position of query 0
+  const int p0 = split * pages_per_split;
+  // the wave's columns are tokens col0 / G .. jlast; the last live one sets how far the wave walks
+  const int col0 = grp * NT * 16, ncol = T * G;
+  const int jlast = min((min(col0 + NT * 16, ncol) - 1) / G, ql - 1);
+  const int wave_limit = col0 < ncol && jlast >= col0 / G ? first + jlast + 1 : 0;  // keys the wave needs
+  const int p1 = min(min(p0 + pages_per_split, (wave_limit + PAGE - 1) / PAGE), bt_width);
+
+  int row[NT], head[NT], limit[NT];
+  bool live[NT];
+#pragma unroll
+  for (int c = 0; c < NT; ++c) {
+    const int col = col0 + 16 * c + qc;
+    const int j = col / G;
+    row[c] = b * T + j;
+    head[c] = kvh * G + (col - j * G);
+    live[c] = col < ncol && j < ql && first + j + 1 > p0 * PAGE;
+    limit[c] = live[c] ? first + j + 1 : 0x7fffffff;
+    if (col >= ncol || row[c] >= rows) row[c] = -1;  // no such row: nothing to write
+  }
+
+  float m[NT], l[NT];
+  f32x4_t acc[NT][8];
+#pragma unroll
+  for (int c = 0; c < NT; ++c) {
+    m[c] = -INFINITY;
+    l[c] = 0.f;
+#pragma unroll
+    for (int n = 0; n < 8; ++n) acc[c][n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  }
+
+  if (p0 < p1) {
+    // Q^T operand: lane (qc, g) holds q[row][head][32kk + 8g .. +8] for k-step kk
+    bf16x8_t qf[NT][4];
+#pragma unroll
+    for (int c = 0; c < NT; ++c) {
+      const bf16_t* qrow = q + (long)(live[c] ? row[c] : 0) * q_stride + (long)(live[c] ? head[c] : 0) * HDIM;
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        qf[c][kk] = ld8(qrow + 32 * kk + 8 * g);
+        if (!live[c]) qf[c][kk] = bf16x8_t{};
+      }
+    }
+    walk_pages<NT, FP8>(k_cache, v_cache, block_tables + (long)b * bt_stride, p0, p1, KVH, kvh, lane, qf,
+                        scale_log2, [&](int c, int key) { return key < limit[c]; }, m, l, acc);
+  }
+  // O^T accumulator: lane (qc, g) holds O[row][head][16n + 4g + i]
+#pragma unroll
+  for (int c = 0; c < NT; ++c) {
+    float ls = l[c];
+    ls += __shfl_xor(ls, 16, 64);
+    ls += __shfl_xor(ls, 32, 64);
+    if (row[c] < 0) continue;
+    const bool some = live[c] && ls > 0.f;
+    if (DIRECT) {
+      if (!some) {
+#pragma unroll
+        for (int n = 0; n < 8; ++n) acc[c][n] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+      }
+      store_o_bf16(out + (long)row[c] * H * HDIM + (long)head[c] * HDIM, acc[c], some ? v_scale / ls : 0.f, g);
+    } else {
+      const long idx = ((long)row[c] * H + head[c]) * nsplit + split;
+      if (g == 0) lse_part[idx] = some ? m[c] + __log2f(ls) : -INFINITY;
+      if (some) {  // an empty split writes only its -inf lse; the combine never reads its o
+        float* o = o_part + idx * HDIM;
+        const float inv = v_scale / ls;
+#pragma unroll
+        for (int n = 0; n < 8; ++n) *reinterpret_cast<f32x4_t*>(o + 16 * n + 4 * g) = acc[c][n] * inv;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Sampling: one workgroup per row of logits [rows][V] (bf16, row stride `stride`).
 // temperature <= 0 -> greedy argmax; otherwise Gumbel-max over logits / T (exactly a draw from
 // softmax(logits / T)) with a counter-based hash of (seed, step, index).  Also returns the chosen
@@ -424,6 +535,54 @@ extern "C" hipError_t dsa_paged_decode(const void* q, long q_stride, const void*
 #undef DSA_PAGED
   DSA_CHECK(hipGetLastError());
   paged_combine_kernel<<<B * H, 256, 0, st>>>(o_part, lse_part, (bf16_t*)out, H, nsplit);
+  return hipGetLastError();
+}
+
+// tiles per wave and waves per (sequence, KV head) for T tokens of G query heads each
+extern "C" void dsa_paged_verify_plan(int T, int G, int* tiles_per_wave, int* groups) {
+  const int tiles = (T * G + 15) / 16;
+  *groups = (tiles + 2) / 3;
+  *tiles_per_wave = (tiles + *groups - 1) / *groups;
+}
+
+// rows = rows of q and out (>= B*T; the rows from B*T on are written as zeros)
+extern "C" hipError_t dsa_paged_verify(const void* q, long q_stride, int rows, const void* k_cache,
+                                       const void* v_cache, const int* block_tables, int bt_stride, int bt_width,
+                                       const int* ctx_lens, const int* q_lens, void* out, float* o_part,
+                                       float* lse_part, int B, int T, int H, int KVH, int nsplit,
+                                       int pages_per_split, float scale, int fp8, float k_scale, float v_scale,
+                                       hipStream_t st) {
+  if (rows <= 0) return hipSuccess;
+  if (KVH <= 0 || H % KVH || H / KVH > 16 || T < 1 || T > 8 || B < 0 || (long)B * T > rows || nsplit < 1 ||
+      pages_per_split < 1 || bt_width < 1)
+    return hipErrorInvalidValue;
+  const int G = H / KVH;
+  const int Bp = (rows + T - 1) / T;  // sequences, the row bucket's padding included
+  int NT, ngroups;
+  dsa_paged_verify_plan(T, G, &NT, &ngroups);
+  const float sl2 = scale * 1.4426950408889634f * (fp8 ? k_scale : 1.f);
+  const float vs = fp8 ? v_scale : 1.f;
+  const dim3 grid(ngroups * Bp * KVH, nsplit);
+#define DSA_VERIFY(N, D, F8)                                                                                   \
+  paged_verify_kernel<N, D, F8><<<grid, 64, 0, st>>>(                                                          \
+      (const bf16_t*)q, q_stride, rows, k_cache, v_cache, block_tables, bt_stride, bt_width, ctx_lens, q_lens, \
+      D ? (bf16_t*)out : nullptr, D ? nullptr : o_part, D ? nullptr : lse_part, B, Bp, T, H, KVH, G, nsplit,   \
+      pages_per_split, sl2, vs)
+#define DSA_VERIFY_NT(D, F8)        \
+  switch (NT) {                     \
+    case 1: DSA_VERIFY(1, D, F8); break; \
+    case 2: DSA_VERIFY(2, D, F8); break; \
+    default: DSA_VERIFY(3, D, F8); break; \
+  }
+  if (nsplit == 1) {
+    if (fp8) { DSA_VERIFY_NT(true, true) } else { DSA_VERIFY_NT(true, false) }
+    return hipGetLastError();
+  }
+  if (fp8) { DSA_VERIFY_NT(false, true) } else { DSA_VERIFY_NT(false, false) }
+#undef DSA_VERIFY_NT
+#undef DSA_VERIFY
+  DSA_CHECK(hipGetLastError());
+  paged_combine_kernel<<<rows * H, 256, 0, st>>>(o_part, lse_part, (bf16_t*)out, H, nsplit);
   return hipGetLastError();
 }
 

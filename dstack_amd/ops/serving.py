@@ -152,6 +152,85 @@ def paged_decode_ref(q, k_cache, v_cache, block_tables, ctx_lens, n_heads, n_kv_
 
 
 # ----------------------------------------------------------------------------------------------
+# Paged verify attention (speculative decoding: a few new query tokens per sequence)
+# ----------------------------------------------------------------------------------------------
+VERIFY_MAX_T = 8
+
+
+def verify_plan(T: int, group: int):
+    """(column tiles per wave, waves per (sequence, KV head)) of the verify kernel: the ``T * group``
+    (token, query head) columns of a KV head in tiles of 16, at most 3 tiles on a wave."""
+    tiles = (T * group + 15) // 16
+    groups = (tiles + 2) // 3
+    return (tiles + groups - 1) // groups, groups
+
+
+class VerifyWorkspace:
+    """Preallocated split-KV partials of :func:`paged_verify` for ``rows`` query rows (a batch bucket
+    of the engine) of ``T`` rows per sequence -- the :class:`DecodeWorkspace` of the verify step."""
+
+    def __init__(self, rows: int, T: int, n_heads: int, n_kv_heads: int, table_width: int, device,
+                 target_waves: int = 2048):
+        if not 1 <= T <= VERIFY_MAX_T:
+            raise ValueError(f"paged_verify takes 1..{VERIFY_MAX_T} query tokens per sequence, got {T}")
+        self.rows, self.T = rows, T
+        seqs = (rows + T - 1) // T
+        self.nsplit, self.pps = split_plan(seqs * verify_plan(T, n_heads // n_kv_heads)[1], n_kv_heads, table_width,
+                                           target_waves)
+        n = rows * n_heads * self.nsplit if self.nsplit > 1 else 1
+        self.o_part = torch.empty(n * HEAD_DIM, dtype=torch.float32, device=device)
+        self.lse_part = torch.empty(n, dtype=torch.float32, device=device)
+
+
+def paged_verify(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_tables: torch.Tensor,
+                 ctx_lens: torch.Tensor, q_lens: torch.Tensor, T: int, n_heads: int, n_kv_heads: int,
+                 out: torch.Tensor | None = None, ws: VerifyWorkspace | None = None, k_scale: float = 1.0,
+                 v_scale: float = 1.0) -> torch.Tensor:
+    """Attention of up to ``T`` (1..8) new query tokens per sequence over its cached keys/values.
+
+    ``q`` [R, >= H*128] with ``R >= B*T`` (rows may be the fused qkv output); row ``b*T + j`` is query
+    j of sequence b.  ``block_tables`` [B, W], ``ctx_lens`` [B], ``q_lens`` [B] int32 with
+    ``0 <= q_lens[b] <= min(T, ctx_lens[b])``: query ``j < q_lens[b]`` sits at position
+    ``ctx_lens[b] - q_lens[b] + j`` and attends to cache keys 0 .. that position -- its own K/V and
+    the earlier queries' are in the cache already (``rope_cache_write``).  Returns [R, H*128]; the rows
+    ``j >= q_lens[b]`` and the rows from ``B*T`` on are zeros."""
+    R = q.shape[0]
+    if out is None:
+        out = torch.empty(R, n_heads * HEAD_DIM, dtype=q.dtype, device=q.device)
+    if _ext.use_hip(q):
+        if ws is None:
+            ws = VerifyWorkspace(R, T, n_heads, n_kv_heads, block_tables.shape[1], q.device)
+        _ext.require().paged_verify(q, k_cache, v_cache, block_tables, ctx_lens, q_lens, out, ws.o_part, ws.lse_part,
+                                    T, n_heads, n_kv_heads, ws.nsplit, ws.pps, 1.0 / math.sqrt(HEAD_DIM), k_scale,
+                                    v_scale)
+        return out
+    out.copy_(paged_verify_ref(q, k_cache, v_cache, block_tables, ctx_lens, q_lens, T, n_heads, n_kv_heads, k_scale,
+                               v_scale).to(out.dtype))
+    return out
+
+
+def paged_verify_ref(q, k_cache, v_cache, block_tables, ctx_lens, q_lens, T, n_heads, n_kv_heads,
+                     k_scale: float = 1.0, v_scale: float = 1.0):
+    """fp32 reference of :func:`paged_verify`: [R, H*128] with zeros in the rows that hold no query.
+    Every query row is computed with the operations of :func:`paged_decode_ref` over its own keys, so
+    it has the bits the decode reference gives that token."""
+    G = n_heads // n_kv_heads
+    out = torch.zeros(q.shape[0], n_heads * HEAD_DIM, dtype=torch.float32, device=q.device)
+    for b in range(block_tables.shape[0]):
+        ctx, n = int(ctx_lens[b]), int(q_lens[b])
+        if n <= 0:
+            continue
+        for j in range(n):
+            m = ctx - n + j + 1  # keys 0 .. its own position
+            k, v = _gather_kv(k_cache, v_cache, block_tables[b], m, n_kv_heads, k_scale, v_scale)
+            qb = q[b * T + j, : n_heads * HEAD_DIM].float().view(n_kv_heads, G, HEAD_DIM)
+            s = torch.einsum("hgd,hnd->hgn", qb, k) / math.sqrt(HEAD_DIM)
+            p = torch.softmax(s, dim=-1)
+            out[b * T + j] = torch.einsum("hgn,hnd->hgd", p, v).reshape(-1)
+    return out
+
+
+# ----------------------------------------------------------------------------------------------
 # Paged-prefix prefill attention (prefix caching: new tokens over a cached prefix)
 # ----------------------------------------------------------------------------------------------
 def paged_prefill(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_tables: torch.Tensor,

@@ -37,6 +37,14 @@ def main(argv=None):
                          "by its `model`; not with --quantization fp8 / mxfp4 or tensor parallel")
     ap.add_argument("--max-lora-rank", type=int, default=64,
                     help="largest adapter rank accepted (the adapter stacks are padded to 8, 16, 32 or 64)")
+    ap.add_argument("--speculative-ngram", type=int, default=0, metavar="K",
+                    help="n-gram speculative decoding: verify up to K (1..7) draft tokens per sequence and step, "
+                         "copied from the latest earlier occurrence of the sequence's last tokens; outputs are the "
+                         "plain engine's; not with --lora-modules or tensor parallel")
+    ap.add_argument("--ngram-max", type=int, default=3, help="longest suffix the proposal matches")
+    ap.add_argument("--ngram-min", type=int, default=1, help="shortest suffix the proposal matches")
+    ap.add_argument("--speculative-max-batch", type=int, default=32,
+                    help="decode steps with more running sequences than this run without drafts")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
     log = logging.getLogger("dstack_amd.serving")
@@ -60,7 +68,9 @@ def main(argv=None):
                                max_prefill_tokens=args.max_prefill_tokens, use_graphs=not args.no_graphs and None,
                                gpu_memory_utilization=args.gpu_memory_utilization, quantization=args.quantization,
                                kv_cache_dtype=args.kv_cache_dtype, enable_prefix_caching=args.enable_prefix_caching,
-                               lora_modules=lora_modules or None, max_lora_rank=args.max_lora_rank)
+                               lora_modules=lora_modules or None, max_lora_rank=args.max_lora_rank,
+                               speculative_ngram=args.speculative_ngram, ngram_max=args.ngram_max,
+                               ngram_min=args.ngram_min, speculative_max_batch=args.speculative_max_batch)
     eng.capture_graphs()
     m = eng.model
     log.info("model %s: %.1f GB weights, %d KV pages (%d tokens), max_model_len %d, %d decode graphs, ready in %.1fs",

@@ -58,6 +58,7 @@ struct Seq {
   int chained = 0;           // leading pages that are hits or registered: the next page to register
   uint64_t chain_hash = 0;   // hash of page chained - 1
   bool chain_open = true;    // false once a page of this sequence could not be registered
+  int spec_pages = 0;        // trailing pages taken for lookahead slots (speculative decoding)
   uint64_t salt = 0;         // seeds the hash chain; pages are shared only among equal salts
 };
 
@@ -157,9 +158,19 @@ class Scheduler {
   //            padded token buffer), rows (total padded rows), positions [rows], slots [rows] (-1 on
   //            padding rows); with prefix caching also block_tables [n, width] and ctx_lens [n]
   //   decode:  positions [n], slots [n], ctx_lens [n], block_tables [n, width]
-  py::dict schedule(bool prefer_decode) {
+  // lookahead = K > 0 (speculative decoding): a decode plan also grants every sequence up to K
+  // token slots after its mandatory one, for draft tokens -- as many as stay below its token cap
+  // and fit in its own pages plus the pages that are FREE once every running sequence has its
+  // mandatory page (never an evicted or a preempted one).  positions and slots are then [n, K + 1]
+  // (slot -1, position 0 beyond the grant), with lookahead [n] the grants; ctx_lens counts no
+  // draft.  A page taken for a grant and not needed by the tokens the step kept goes back to the
+  // free list at the next call, before anything is planned: speculation never causes a preemption
+  // or an eviction.
+  py::dict schedule(bool prefer_decode, int lookahead) {
+    if (lookahead < 0) throw std::invalid_argument("scheduler: lookahead must be >= 0");
     py::dict out;
     std::vector<int64_t> preempted;
+    for (auto id : running_) return_lookahead_pages(get(id));
     // admission of waiting sequences (prefill-first unless the caller asks to run decodes)
     const bool can_admit = !waiting_.empty() && (int)running_.size() < max_batch_;
     if (can_admit && !(prefer_decode && !running_.empty())) {
@@ -266,24 +277,55 @@ class Scheduler {
       out["preempted"] = preempted;
       return out;
     }
-    py::array_t<int32_t> positions(n), slots(n), ctx(n);
+    py::array_t<int32_t> ctx(n);
     py::array_t<int32_t> tables({n, table_width_});
-    auto ps = positions.mutable_unchecked<1>();
-    auto sl = slots.mutable_unchecked<1>();
     auto cx = ctx.mutable_unchecked<1>();
     auto tb = tables.mutable_unchecked<2>();
+    if (lookahead > 0) {
+      const int K1 = lookahead + 1;
+      py::array_t<int32_t> grants(n);
+      py::array_t<int32_t> positions({n, K1}), slots({n, K1});
+      auto gr = grants.mutable_unchecked<1>();
+      auto ps = positions.mutable_unchecked<2>();
+      auto sl = slots.mutable_unchecked<2>();
+      for (int i = 0; i < n; ++i) {
+        Seq& s = get(running_[i]);
+        // the step emits at most grant + 1 tokens: they must fit under the cap
+        int grant = std::max(0, std::min(lookahead, s.max_tokens - s.num_tokens - 1));
+        const int room = ((int)s.pages.size() + (int)free_.size()) * page_size_ - s.num_tokens;
+        grant = std::min(grant, std::max(0, room));
+        const int before = (int)s.pages.size();
+        grow(s, s.num_tokens + grant);  // (from free_ only: room counted no cached page)
+        s.spec_pages = (int)s.pages.size() - before;
+        gr(i) = grant;
+        for (int j = 0; j < K1; ++j) {
+          ps(i, j) = j <= grant ? s.num_tokens - 1 + j : 0;
+          sl(i, j) = j <= grant ? slot_of(s, s.num_tokens - 1 + j) : -1;
+        }
+      }
+      out["lookahead"] = grants;
+      out["positions"] = positions;
+      out["slots"] = slots;
+    } else {
+      py::array_t<int32_t> positions(n), slots(n);
+      auto ps = positions.mutable_unchecked<1>();
+      auto sl = slots.mutable_unchecked<1>();
+      for (int i = 0; i < n; ++i) {
+        const Seq& s = get(running_[i]);
+        ps(i) = s.num_tokens - 1;
+        sl(i) = slot_of(s, s.num_tokens - 1);
+      }
+      out["positions"] = positions;
+      out["slots"] = slots;
+    }
     for (int i = 0; i < n; ++i) {
       const Seq& s = get(running_[i]);
-      ps(i) = s.num_tokens - 1;
-      sl(i) = slot_of(s, s.num_tokens - 1);
       cx(i) = s.num_tokens;
       const int np = (int)s.pages.size();
       for (int j = 0; j < table_width_; ++j) tb(i, j) = j < np ? s.pages[j] : 0;
     }
     out["kind"] = "decode";
     out["seq_ids"] = running_;
-    out["positions"] = positions;
-    out["slots"] = slots;
     out["ctx_lens"] = ctx;
     out["block_tables"] = tables;
     out["preempted"] = preempted;
@@ -331,7 +373,18 @@ class Scheduler {
       if (caching_) info_[p].ref = 1;
     }
   }
+  // the lookahead pages of the last plan that the tokens kept since do not reach
+  void return_lookahead_pages(Seq& s) {
+    for (; s.spec_pages > 0 && (int)s.pages.size() > pages_for(s.num_tokens); --s.spec_pages) {
+      const int32_t p = s.pages.back();  // (beyond num_cached: never registered)
+      s.pages.pop_back();
+      if (caching_) info_[p].ref = 0;
+      free_.push_back(p);
+    }
+    s.spec_pages = 0;
+  }
   void release(Seq& s) {
+    s.spec_pages = 0;
     if (!caching_) {
       for (auto p : s.pages) free_.push_back(p);
     } else {
@@ -478,6 +531,33 @@ class Scheduler {
   std::vector<int64_t> running_;
 };
 
+// N-gram ("prompt lookup") proposal for speculative decoding: for n = n_max .. n_min, the most
+// recent earlier occurrence of the last n tokens of `ids` (starting at s <= len - n - 1); on the
+// first n that matches, the k tokens that followed it.  The copy may run over the end of the history
+// into the drafts already produced (a loop of period p therefore yields k drafts).  No match: empty.
+py::array_t<int32_t> ngram_propose(const py::array_t<int32_t, py::array::c_style | py::array::forcecast>& ids, int k,
+                                   int n_max, int n_min) {
+  if (ids.ndim() != 1) throw std::invalid_argument("ngram_propose: ids must be one-dimensional");
+  if (k < 0 || n_min < 1 || n_max < n_min) throw std::invalid_argument("ngram_propose: need k >= 0, 1 <= n_min <= n_max");
+  const int32_t* x = ids.data();
+  const long len = (long)ids.shape(0);
+  for (long n = n_max; n >= n_min && k > 0; --n) {
+    if (len < n + 1) continue;
+    const int32_t* suffix = x + len - n;
+    for (long s = len - n - 1; s >= 0; --s) {
+      if (!std::equal(suffix, suffix + n, x + s)) continue;
+      py::array_t<int32_t> out(k);
+      int32_t* d = out.mutable_data();
+      for (long i = 0; i < k; ++i) {
+        const long src = s + n + i;
+        d[i] = src < len ? x[src] : d[src - len];
+      }
+      return out;
+    }
+  }
+  return py::array_t<int32_t>(0);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_sched, m) {
@@ -493,7 +573,7 @@ PYBIND11_MODULE(_sched, m) {
       .def("mark_computed", &Scheduler::mark_computed)
       .def("finish", &Scheduler::finish)
       .def("is_done", &Scheduler::is_done)
-      .def("schedule", &Scheduler::schedule, py::arg("prefer_decode") = false)
+      .def("schedule", &Scheduler::schedule, py::arg("prefer_decode") = false, py::arg("lookahead") = 0)
       .def("pages", &Scheduler::pages)
       .def("num_tokens", &Scheduler::num_tokens)
       .def_property_readonly("free_pages", &Scheduler::free_pages)
@@ -506,4 +586,5 @@ PYBIND11_MODULE(_sched, m) {
       .def_property_readonly("num_running", &Scheduler::num_running)
       .def_property_readonly("table_width", &Scheduler::table_width)
       .def_property_readonly("page_size", &Scheduler::page_size);
+  m.def("ngram_propose", &ngram_propose, py::arg("ids"), py::arg("k"), py::arg("n_max") = 3, py::arg("n_min") = 1);
 }

@@ -99,6 +99,9 @@ class Request:
         return self.prompt_ids + self.output_ids
 
 
+VERIFY_MAX_ROWS = 256  # the largest row count of a verify step (the decode GEMMs are tuned up to it)
+
+
 def _buckets(max_batch: int):
     out, b = [], 1
     while b < max_batch:
@@ -112,11 +115,18 @@ class LLMEngine:
     def __init__(self, model: ServingLlama, max_batch: int = 256, max_prefill_tokens: int = 16384,
                  num_pages: int | None = None, use_graphs: bool | None = None, gpu_memory_utilization: float = 0.90,
                  eos_token_ids=(), enable_prefix_caching: bool = False, lora_modules: dict | None = None,
-                 max_lora_rank: int = 64):
+                 max_lora_rank: int = 64, speculative_ngram: int = 0, ngram_max: int = 3, ngram_min: int = 1,
+                 speculative_max_batch: int = 32):
         from dstack_amd.serving import _native
 
         if enable_prefix_caching and model.tp > 1:
             raise ValueError("prefix caching is not supported with tensor parallel yet")
+        _check_speculative(speculative_ngram, ngram_max, ngram_min, speculative_max_batch,
+                           model.tp > 1, lora_modules)
+        # n-gram speculative decoding: K drafts per sequence, T = K + 1 rows of a verify step
+        self.spec_k, self.spec_T = int(speculative_ngram), int(speculative_ngram) + 1
+        self.ngram_max, self.ngram_min, self.spec_max_batch = int(ngram_max), int(ngram_min), int(speculative_max_batch)
+        self._propose = _native.ngram_propose
         # LoRA adapters ({name: PEFT directory}): every adapter gets its own slot of the model's
         # stacks, loaded here -- before the KV cache is sized -- and kept for the engine's life
         self.lora_slots: dict[str, int] = {}
@@ -162,8 +172,19 @@ class LLMEngine:
         # -> graph of the step with the LoRA kernels (a step whose rows all run the base model
         # replays the plain one)
         self._graphs: dict = {}
+        # verify steps (speculative decoding): n sequences take n * T rows, padded to the smallest row
+        # count of the bucket series -- every GEMM then runs at a row count the decode step already
+        # has a tuned path for; with captured graphs also ("verify", R) -> graph
+        self.verify_buckets = []
+        if self.spec_k:
+            series = [r for r in _buckets(VERIFY_MAX_ROWS)]
+            want = {next((r for r in series if r >= n * self.spec_T), None)
+                    for n in range(1, min(self.spec_max_batch, max_batch) + 1)}
+            self.verify_buckets = sorted(r for r in want if r is not None)
         self._alloc_static()
         self.stats = dict(prefill_tokens=0, decode_tokens=0, steps=0, preemptions=0, prefill_s=0.0, decode_s=0.0)
+        if self.spec_k:
+            self.stats.update(spec_steps=0, spec_drafted=0, spec_accepted=0)
         if self.prefix_caching:
             # (prefill_tokens counts computed tokens: an admitted prompt is its hit + computed tokens)
             self.stats.update(prefix_hit_tokens=0, prefix_query_tokens=0, prefix_cached_pages=0)
@@ -175,6 +196,8 @@ class LLMEngine:
             raise ValueError("prefix caching is not supported with tensor parallel yet")
         if kw.get("lora_modules"):
             _check_lora(quantization, tp_group)  # before any weight is loaded
+        _check_speculative(kw.get("speculative_ngram", 0), kw.get("ngram_max", 3), kw.get("ngram_min", 1),
+                           kw.get("speculative_max_batch", 32), tp_group is not None, kw.get("lora_modules"))
         if quantization == "mxfp4" and tp_group is not None:
             raise ValueError("quantization=\"mxfp4\" is not supported with tensor parallel yet")
         spec = load_spec(model)
@@ -194,25 +217,27 @@ class LLMEngine:
     # ------------------------------------------------------------------------------------------
     def _alloc_static(self):
         dev, B, W = self.device, self.max_batch, self.width
+        # rows of the per-row buffers: a verify step (speculative decoding) has T rows per sequence
+        N = self.rows_max = max([B] + self.verify_buckets)
         i32 = dict(dtype=torch.int32, device=dev)
-        self.s_tokens = torch.zeros(B, dtype=torch.int64, device=dev)
-        self.s_pos = torch.zeros(B, **i32)
-        self.s_slots = torch.full((B,), -1, **i32)
+        self.s_tokens = torch.zeros(N, dtype=torch.int64, device=dev)
+        self.s_pos = torch.zeros(N, **i32)
+        self.s_slots = torch.full((N,), -1, **i32)
         self.s_tables = torch.zeros(B, W, **i32)
         self.s_ctx = torch.zeros(B, **i32)
-        self.s_temps = torch.zeros(B, dtype=torch.float32, device=dev)
-        self.s_seeds = torch.zeros(B, dtype=torch.int64, device=dev)
-        self.s_steps = torch.zeros(B, **i32)
-        self.s_out_tok = torch.zeros(B, **i32)
-        self.s_out_lp = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.s_temps = torch.zeros(N, dtype=torch.float32, device=dev)
+        self.s_seeds = torch.zeros(N, dtype=torch.int64, device=dev)
+        self.s_steps = torch.zeros(N, **i32)
+        self.s_out_tok = torch.zeros(N, **i32)
+        self.s_out_lp = torch.zeros(N, dtype=torch.float32, device=dev)
         # truncation and top-N log-probabilities (padding rows: k = 0, p = 1, min_p = 0, top_n = 0)
-        self.s_top_k = torch.zeros(B, **i32)
-        self.s_top_p = torch.ones(B, dtype=torch.float32, device=dev)
-        self.s_min_p = torch.zeros(B, dtype=torch.float32, device=dev)
-        self.s_top_n = torch.zeros(B, **i32)
-        self.s_tau = torch.zeros(B, dtype=torch.float32, device=dev)
-        self.s_top_ids = torch.full((B, sops.TOP_LOGPROBS_MAX), -1, **i32)
-        self.s_top_lps = torch.full((B, sops.TOP_LOGPROBS_MAX), float("-inf"), dtype=torch.float32, device=dev)
+        self.s_top_k = torch.zeros(N, **i32)
+        self.s_top_p = torch.ones(N, dtype=torch.float32, device=dev)
+        self.s_min_p = torch.zeros(N, dtype=torch.float32, device=dev)
+        self.s_top_n = torch.zeros(N, **i32)
+        self.s_tau = torch.zeros(N, dtype=torch.float32, device=dev)
+        self.s_top_ids = torch.full((N, sops.TOP_LOGPROBS_MAX), -1, **i32)
+        self.s_top_lps = torch.full((N, sops.TOP_LOGPROBS_MAX), float("-inf"), dtype=torch.float32, device=dev)
         self._filter_rows_set = 0  # leading rows of the four parameter buffers that may hold a request's values
         # penalties and logit_bias: one state row and bias list per running sequence that asked (a
         # request takes a slot when its prompt is sampled and gives it back when it finishes or is
@@ -220,15 +245,19 @@ class LLMEngine:
         # (tensor parallel: only the leader samples, so only the leader holds state)
         self.p_state, self.p_bias_ids, self.p_bias_vals, self.p_bias_n = sops.alloc_penalty_state(
             B if self.leader else 1, self.model.cfg.vocab_size, dev)
-        self.s_pen_slot = torch.full((B,), -1, **i32)
-        self.s_pen = torch.empty(4, B, dtype=torch.float32, device=dev)  # rows: rep, 1 / rep, freq, pres
-        self._reset_penalty_rows(B)
+        self.s_pen_slot = torch.full((N,), -1, **i32)
+        self.s_pen = torch.empty(4, N, dtype=torch.float32, device=dev)  # rows: rep, 1 / rep, freq, pres
+        self._reset_penalty_rows(N)
         self._pen_free = list(range(B - 1, -1, -1))
         self._pen_slots: dict[int, int] = {}  # request id -> slot
         # LoRA: every row's adapter slot (padding rows and base-model rows: -1)
         self.s_lora_idx = torch.full((B,), -1, **i32)
         self._lora_rows_set = 0  # leading rows of s_lora_idx that may hold a slot
         self._ws = {b: sops.DecodeWorkspace(b, self.model.H, self.model.KVH, W, dev) for b in self.buckets}
+        if self.spec_k:
+            self.s_qlens = torch.zeros(B, **i32)  # rows in use per sequence of a verify step
+            self._vws = {r: sops.VerifyWorkspace(r, self.spec_T, self.model.H, self.model.KVH, W, dev)
+                         for r in self.verify_buckets}
 
     def _reset_penalty_rows(self, m: int):
         self.s_pen_slot[:m].fill_(-1)
@@ -251,6 +280,23 @@ class LLMEngine:
         sops.penalties_update(self.p_state, self.s_pen_slot[:b], self.s_out_tok[:b])
         return logits
 
+    def _verify_seqs(self, R: int) -> int:
+        """Sequences a verify step of R rows holds (its block-table rows)."""
+        return min(R // self.spec_T, self.max_batch)
+
+    def _verify_body(self, R: int):
+        """The decode body over R rows, T per sequence, with the verify attention."""
+        nb = self._verify_seqs(R)
+        logits = self.model.verify(self.s_tokens[:R], self.s_pos[:R], self.s_slots[:R], self.s_tables[:nb],
+                                   self.s_ctx[:nb], self.s_qlens[:nb], self.spec_T, ws=self._vws[R])
+        self._apply_penalties(logits, self.s_pen_slot[:R], self.s_pen[:, :R])
+        sops.sample_filtered(logits, self.s_temps[:R], self.s_seeds[:R], self.s_steps[:R], self.s_top_k[:R],
+                             self.s_top_p[:R], self.s_min_p[:R], self.s_out_tok[:R], self.s_out_lp[:R],
+                             top_n=self.s_top_n[:R], top_ids=self.s_top_ids[:R], top_lps=self.s_top_lps[:R],
+                             tau=self.s_tau[:R])
+        sops.penalties_update(self.p_state, self.s_pen_slot[:R], self.s_out_tok[:R])
+        return logits
+
     def capture_graphs(self):
         """One hipGraph per batch bucket (largest first, sharing one memory pool)."""
         if not self.use_graphs or self._graphs:
@@ -263,9 +309,11 @@ class LLMEngine:
         self.s_min_p.zero_()
         self.s_top_n.zero_()
         self._filter_rows_set = 0
-        self._reset_penalty_rows(self.max_batch)
+        self._reset_penalty_rows(self.rows_max)
         self.s_lora_idx.fill_(-1)
         self._lora_rows_set = 0
+        if self.spec_k:
+            self.s_qlens.zero_()
         variants = [False, True] if self.lora_slots else [False]
         torch.cuda.synchronize(self.device)
         s = torch.cuda.Stream(self.device)
@@ -277,6 +325,8 @@ class LLMEngine:
             for b in self.buckets:
                 for lora in variants:
                     self._decode_body(b, lora)
+            for r in self.verify_buckets:
+                self._verify_body(r)
         torch.cuda.current_stream(self.device).wait_stream(s)
         pool = torch.cuda.graph_pool_handle()
         self._graph_logits = {}
@@ -287,6 +337,11 @@ class LLMEngine:
                 with torch.cuda.graph(g, pool=pool):
                     self._graph_logits[key] = self._decode_body(b, lora)
                 self._graphs[key] = g
+        for r in reversed(self.verify_buckets):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=pool):
+                self._graph_logits["verify", r] = self._verify_body(r)
+            self._graphs["verify", r] = g
         torch.cuda.synchronize(self.device)
 
     # ------------------------------------------------------------------------------------------
@@ -357,7 +412,10 @@ class LLMEngine:
     def step(self) -> int:
         """Run one scheduled step; returns the number of tokens produced."""
         self._admit_pending()
-        plan = self.sched.schedule(False)
+        if self.spec_k and 0 < self.sched.num_running <= self.spec_max_batch:
+            plan = self.sched.schedule(False, self.spec_k)  # a decode plan then grants lookahead slots
+        else:
+            plan = self.sched.schedule(False)
         for rid in plan["preempted"]:
             self.stats["preemptions"] += 1
             self._release_penalty_slot(rid)  # rebuilt when its recompute prefill is sampled
@@ -367,6 +425,9 @@ class LLMEngine:
         ids = list(plan["seq_ids"])
         reqs = [self.requests[i] for i in ids]
         t0 = time.perf_counter()
+        runs = drafts = None
+        if kind == "decode" and "lookahead" in plan and self._verify_rows(len(reqs)) is not None:
+            drafts = [self._drafts(r, int(g)) for r, g in zip(reqs, plan["lookahead"])]
         if kind == "prefill":
             toks = np.zeros(plan["rows"], dtype=np.int64)
             for r, off, n, st in zip(reqs, plan["offsets"], plan["lens"], plan["starts"]):
@@ -392,7 +453,13 @@ class LLMEngine:
                 self.stats.update(prefix_hit_tokens=self.sched.prefix_hit_tokens,
                                   prefix_query_tokens=self.sched.prefix_query_tokens)
             self.stats["prefill_s"] += time.perf_counter() - t0
+        elif drafts is not None and any(drafts):
+            tokens, lps, tops, runs = self._verify(plan, reqs, drafts)
+            self.stats["decode_s"] += time.perf_counter() - t0
         else:
+            if "lookahead" in plan:  # (no sequence has a draft, or too many rows: the plain step)
+                plan["positions"] = np.ascontiguousarray(plan["positions"][:, 0])
+                plan["slots"] = np.ascontiguousarray(plan["slots"][:, 0])
             tokens, lps, tops = self._decode(plan, reqs)
             self.stats["decode_tokens"] += len(reqs)
             self.stats["decode_s"] += time.perf_counter() - t0
@@ -400,35 +467,48 @@ class LLMEngine:
         if self.prefix_caching:
             self.stats["prefix_cached_pages"] = self.sched.cached_pages
         now = time.perf_counter()
-        for i, (req, tok, lp) in enumerate(zip(reqs, tokens, lps)):
-            self.sched.mark_computed(req.id)
-            if req.finished:  # aborted while the step ran
-                continue
-            tok = int(tok)
-            req.output_ids.append(tok)
-            req.logprobs.append(float(lp))
-            if req.params.top_logprobs > 0:
-                req.top_logprobs.append([(t, l) for t, l in zip(tops[0][i], tops[1][i]) if t >= 0])
-            if req.first_token_at is None:
-                req.first_token_at = now
-            if self.prefix_caching:
-                self.sched.append(req.id, tok)
-            else:
-                self.sched.append(req.id)
-            reason = None
-            if len(req.output_ids) >= req.params.max_tokens:
-                reason = "length"
-            elif not req.params.ignore_eos and (tok in self.eos_token_ids or tok in req.params.stop_token_ids):
-                reason = "stop"
-            elif len(req.all_ids) >= self.model.max_model_len:
-                reason = "length"
-            if reason:
-                req.finished, req.finish_reason, req.finished_at = True, reason, now
-                self.sched.finish(req.id)
-                self._release_penalty_slot(req.id)
-            self._emit(req, tok, req.finished)
-            if req.finished:
-                self.requests.pop(req.id, None)
+        # the rows of the step's outputs that each request emits, in order: one, or (verify step) the
+        # rows of its accepted drafts and the one after them
+        verify = runs is not None
+        if not verify:
+            runs = [(i,) for i in range(len(reqs))]
+        emitted = 0
+        for req, rows in zip(reqs, runs):
+            for i in rows:
+                # (a verify step: the K/V of an accepted draft counts as cached once its token is kept)
+                self.sched.mark_computed(req.id)
+                if req.finished:  # aborted while the step ran
+                    break
+                tok = int(tokens[i])
+                req.output_ids.append(tok)
+                req.logprobs.append(float(lps[i]))
+                if req.params.top_logprobs > 0:
+                    req.top_logprobs.append([(t, l) for t, l in zip(tops[0][i], tops[1][i]) if t >= 0])
+                if req.first_token_at is None:
+                    req.first_token_at = now
+                if self.prefix_caching:
+                    self.sched.append(req.id, tok)
+                else:
+                    self.sched.append(req.id)
+                emitted += 1
+                reason = None
+                if len(req.output_ids) >= req.params.max_tokens:
+                    reason = "length"
+                elif not req.params.ignore_eos and (tok in self.eos_token_ids or tok in req.params.stop_token_ids):
+                    reason = "stop"
+                elif len(req.all_ids) >= self.model.max_model_len:
+                    reason = "length"
+                if reason:
+                    req.finished, req.finish_reason, req.finished_at = True, reason, now
+                    self.sched.finish(req.id)
+                    self._release_penalty_slot(req.id)
+                self._emit(req, tok, req.finished)
+                if req.finished:  # the tokens after a finishing one are dropped
+                    self.requests.pop(req.id, None)
+                    break
+        if verify:
+            self.stats["decode_tokens"] += emitted
+            return emitted
         return len(reqs)
 
     def _seed_rows(self, reqs):
@@ -480,8 +560,10 @@ class LLMEngine:
         """slot int32 [m] and (rep, 1 / rep, freq, pres) fp32 [4, m] of the requests, padded with inert
         rows up to ``rows``; a request without a slot asks for nothing."""
         pad = max(0, (rows or 0) - len(reqs))
-        slot = torch.tensor([self._pen_slots.get(r.id, -1) for r in reqs] + [-1] * pad, dtype=torch.int32)
-        p = [r.params if r.id in self._pen_slots else SamplingParams() for r in reqs]
+        held = [r is not None and r.id in self._pen_slots for r in reqs]  # (None: a row that asks for nothing)
+        slot = torch.tensor([self._pen_slots[r.id] if h else -1 for r, h in zip(reqs, held)] + [-1] * pad,
+                            dtype=torch.int32)
+        p = [r.params if h else SamplingParams() for r, h in zip(reqs, held)]
         rep = torch.tensor([q.repetition_penalty for q in p] + [1.0] * pad, dtype=torch.float32)
         freq = torch.tensor([q.frequency_penalty for q in p] + [0.0] * pad, dtype=torch.float32)
         pres = torch.tensor([q.presence_penalty for q in p] + [0.0] * pad, dtype=torch.float32)
@@ -490,7 +572,7 @@ class LLMEngine:
     def _stage_penalties(self, reqs, b: int):
         """Stage penalty slots and parameters into the static buffers, as ``_stage_filters`` does:
         steps where no request holds a slot (the common case) copy nothing."""
-        if self._pen_slots and any(r.id in self._pen_slots for r in reqs):
+        if self._pen_slots and any(r is not None and r.id in self._pen_slots for r in reqs):
             m = max(b, self._pen_rows_set)
             slot, pen = self._penalty_rows(reqs, m)
             self.s_pen_slot[:m].copy_(slot, non_blocking=True)
@@ -569,6 +651,77 @@ class LLMEngine:
                 self._decode_body(b, lora)
             return (self.s_out_tok[:n].tolist(), self.s_out_lp[:n].tolist(),
                     self._tops(reqs, self.s_top_ids[:n], self.s_top_lps[:n]))
+
+    # ------------------------------------------------------------------------------------------
+    # n-gram speculative decoding
+    # ------------------------------------------------------------------------------------------
+    def _verify_rows(self, n: int):
+        """The row bucket of a verify step of n sequences, or None when it takes too many rows."""
+        return next((r for r in self.verify_buckets if r >= n * self.spec_T), None) if n <= self.spec_max_batch else None
+
+    def _drafts(self, req, grant: int):
+        """The draft tokens of ``req`` for a step: the n-gram proposal over its tokens so far, at most
+        ``grant`` of them.  None for a request that asks for a penalty or a logit_bias (it holds a state slot, whose
+        counts depend on every earlier token)."""
+        if grant <= 0 or req.params.wants_penalties:
+            return []
+        return self._propose(np.asarray(req.all_ids, dtype=np.int32), grant, self.ngram_max, self.ngram_min).tolist()
+
+    def _verify(self, plan, reqs, drafts):
+        """One verify step: row ``b*T`` carries sequence b's last token and rows ``b*T + 1 ..`` its
+        drafts; every row is sampled as the plain step would sample that position, and a draft is
+        accepted iff it is the token drawn from the row before it.  Returns the step's flat outputs
+        and, per request, the rows it emits (its accepted drafts' rows and the one after them)."""
+        n, T = len(reqs), self.spec_T
+        R = self._verify_rows(n)
+        nb = self._verify_seqs(R)
+        tokens, pos = np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int32)
+        slots = np.full(R, -1, dtype=np.int32)
+        temps, seeds, steps = np.zeros(R, dtype=np.float32), np.zeros(R, dtype=np.int64), np.zeros(R, dtype=np.int32)
+        ctx, qlens = np.zeros(nb, dtype=np.int32), np.zeros(nb, dtype=np.int32)
+        for b, (r, d) in enumerate(zip(reqs, drafts)):
+            q = 1 + len(d)
+            rows = slice(b * T, b * T + q)
+            tokens[rows] = [r.all_ids[-1]] + d
+            pos[rows] = plan["positions"][b, :q]
+            slots[rows] = plan["slots"][b, :q]
+            temps[rows] = r.params.temperature
+            seeds[rows] = r.seed
+            steps[rows] = len(r.output_ids) + np.arange(q)
+            ctx[b] = plan["ctx_lens"][b] + len(d)
+            qlens[b] = q
+        # per-row sampler inputs: a sequence's filters on all of its rows, its penalty slot on its first
+        row_reqs = [r for r in reqs for _ in range(T)]
+        pen_reqs = [r if j == 0 else None for r in reqs for j in range(T)]
+        nbf = torch.from_numpy
+        with torch.no_grad():
+            self.s_tokens[:R].copy_(nbf(tokens), non_blocking=True)
+            self.s_pos[:R].copy_(nbf(pos), non_blocking=True)
+            self.s_slots[:R].copy_(nbf(slots), non_blocking=True)
+            self.s_tables[:n].copy_(nbf(plan["block_tables"]), non_blocking=True)
+            self.s_ctx[:nb].copy_(nbf(ctx), non_blocking=True)
+            self.s_qlens[:nb].copy_(nbf(qlens), non_blocking=True)
+            self.s_temps[:R].copy_(nbf(temps), non_blocking=True)
+            self.s_seeds[:R].copy_(nbf(seeds), non_blocking=True)
+            self.s_steps[:R].copy_(nbf(steps), non_blocking=True)
+            self._stage_filters(row_reqs, R)
+            self._stage_penalties(pen_reqs, R)
+            if ("verify", R) in self._graphs:
+                self._graphs["verify", R].replay()
+            else:
+                self._verify_body(R)
+            out_tok, out_lp = self.s_out_tok[:R].tolist(), self.s_out_lp[:R].tolist()
+            tops = self._tops(reqs, self.s_top_ids[:R], self.s_top_lps[:R])
+        runs = []
+        for b, d in enumerate(drafts):
+            a = 0
+            while a < len(d) and out_tok[b * T + a] == d[a]:
+                a += 1
+            runs.append(tuple(range(b * T, b * T + a + 1)))
+            self.stats["spec_drafted"] += len(d)
+            self.stats["spec_accepted"] += a
+        self.stats["spec_steps"] += 1
+        return out_tok, out_lp, tops, runs
 
     # ------------------------------------------------------------------------------------------
     # tensor parallel: the leader broadcasts each step's inputs, followers replay them
@@ -697,6 +850,25 @@ def _check_lora(quantization, tp_group):
                          "projections (an fp8 KV cache is fine)")
     if tp_group is not None:
         raise ValueError("LoRA adapters are not supported with tensor parallel yet")
+
+
+def _check_speculative(speculative_ngram, ngram_max, ngram_min, speculative_max_batch, tensor_parallel, lora_modules):
+    """The option values and combinations n-gram speculative decoding is refused with."""
+    k = speculative_ngram
+    if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= sops.VERIFY_MAX_T - 1:
+        raise ValueError(f"speculative_ngram must be 0 (off) or in [1, {sops.VERIFY_MAX_T - 1}], got {k!r}")
+    for name, v in (("ngram_min", ngram_min), ("ngram_max", ngram_max), ("speculative_max_batch", speculative_max_batch)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+    if ngram_min > ngram_max:
+        raise ValueError(f"ngram_min must not exceed ngram_max, got ngram_min={ngram_min}, ngram_max={ngram_max}")
+    if k == 0:
+        return
+    if tensor_parallel:
+        raise ValueError("speculative_ngram is not supported with tensor parallel yet")
+    if lora_modules:
+        raise ValueError("speculative_ngram is not supported with lora_modules (--lora-modules) yet: a verify step "
+                         "runs without the adapter kernels")
 
 
 def _filter_top_k_top_p(logits: torch.Tensor, reqs) -> torch.Tensor:

@@ -718,6 +718,12 @@ class ServingLlama:
             C = _ext.require()
             if C.gemv_supported(x.shape[0], x.shape[1]) and x.stride(-1) == 1:
                 return C.gemv(x, w)
+        if not self.hip and x.dtype == torch.float32:
+            # the CPU path (fp32): products accumulated in fp64 and rounded once, so that a row's
+            # result does not depend on how many rows are multiplied with it (the library's fp32 GEMM
+            # picks another summation order from 16 rows on) and a sequence computes the same logits
+            # in a decode step, in a verify step and at any batch size
+            return (x.double() @ w.double().t()).to(x.dtype)
         return x @ w.t()
 
     def _mm_mxfp4(self, x, w: Mxfp4Weight):
@@ -955,6 +961,31 @@ class ServingLlama:
         on its input, ``sops.lora_expand`` into its output)."""
         if lora_idx is not None and not self.lora:
             raise ValueError("decode: lora_idx given but no adapter slots (enable_lora)")
+
+        def attend(qkv, li):
+            return sops.paged_decode(qkv, self.k_cache[li], self.v_cache[li], block_tables, ctx_lens, self.H, self.KVH,
+                                     ws=ws, k_scale=self.k_scale, v_scale=self.v_scale)
+
+        return self._token_rows(tokens, positions, slots, attend, lora_idx)
+
+    @torch.no_grad()
+    def verify(self, tokens, positions, slots, block_tables, ctx_lens, q_lens, T, ws=None):
+        """Speculative decoding's verify step: ``decode`` over R rows, up to ``T`` per sequence.  Row
+        ``b*T + j`` is token j of sequence b (``tokens``, ``positions``, ``slots``: [R]; its last token
+        and then its drafts); ``block_tables`` [B, W], ``ctx_lens`` [B] (drafts included) and ``q_lens``
+        [B] (rows in use) with ``B*T <= R``.  Every row's K/V is written to the cache, then row j
+        attends to its sequence up to its own position (``sops.paged_verify``).  Returns logits
+        [R, vocab]; rows past ``q_lens`` (slot -1) are inert."""
+
+        def attend(qkv, li):
+            return sops.paged_verify(qkv, self.k_cache[li], self.v_cache[li], block_tables, ctx_lens, q_lens, T, self.H,
+                                     self.KVH, ws=ws, k_scale=self.k_scale, v_scale=self.v_scale)
+
+        return self._token_rows(tokens, positions, slots, attend, None)
+
+    def _token_rows(self, tokens, positions, slots, attend, lora_idx):
+        """The layers of a decode or verify step over one token per row; ``attend(qkv, li)`` is the
+        step's attention over layer li's cache."""
         H, KVH = self.H, self.KVH
         x = F.embedding(tokens, self.embed)
         delta = None
@@ -970,8 +1001,7 @@ class ServingLlama:
                 qkv = qkv + L["bqkv"]
             sops.rope_cache_write(qkv, positions, slots, self.cos, self.sin, self.k_cache[li], self.v_cache[li], H, KVH,
                                   self.k_scale, self.v_scale)
-            o = sops.paged_decode(qkv, self.k_cache[li], self.v_cache[li], block_tables, ctx_lens, H, KVH, ws=ws,
-                                  k_scale=self.k_scale, v_scale=self.v_scale)
+            o = attend(qkv, li)
             x, delta = self._mlp_and_attn_out(L, x, o, li, lora_idx)
         _, h = self._add_rms(x, delta, self.norm)
         return self._logits(h)

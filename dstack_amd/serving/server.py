@@ -386,6 +386,11 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
               m["prefix_query_tokens"], "counter")
             g("dstack_serving_prefix_cached_pages", "KV-cache pages registered for prefix reuse (64 tokens each)",
               m["prefix_cached_pages"])
+        if engine.spec_k:
+            g("dstack_serving_spec_steps_total", "verify steps run (n-gram speculative decoding)", m["spec_steps"],
+              "counter")
+            g("dstack_serving_spec_draft_tokens_total", "draft tokens proposed and verified", m["spec_drafted"], "counter")
+            g("dstack_serving_spec_accepted_tokens_total", "draft tokens accepted", m["spec_accepted"], "counter")
         ttft = state["ttft_sum"] / state["ttft_n"] if state["ttft_n"] else 0.0
         g("dstack_serving_ttft_mean_seconds", "mean time to first token", round(ttft, 6))
         return PlainTextResponse("\n".join(lines) + "\n")
