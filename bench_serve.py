@@ -71,6 +71,11 @@ def main():
     ap.add_argument("--ngram-max", type=int, default=3)
     ap.add_argument("--ngram-min", type=int, default=1)
     ap.add_argument("--speculative-max-batch", type=int, default=32)
+    ap.add_argument("--guided", choices=["json_object"], default=None,
+                    help="every request carries this structured-output constraint (a built-in config decodes "
+                         "with the byte tokenizer; a request ends with EOS when its document closes, or at "
+                         "--output-len)")
+    ap.add_argument("--max-guides", type=int, default=16, help="grammar slots (0: structured outputs off)")
     args = ap.parse_args()
     if args.lora_idle and not args.num_loras:
         ap.error("--lora-idle needs --num-loras")
@@ -101,7 +106,7 @@ def main():
                                enable_prefix_caching=args.enable_prefix_caching, lora_modules=lora_modules,
                                max_lora_rank=max(args.lora_rank, 8), speculative_ngram=args.speculative_ngram,
                                ngram_max=args.ngram_max, ngram_min=args.ngram_min,
-                               speculative_max_batch=args.speculative_max_batch)
+                               speculative_max_batch=args.speculative_max_batch, max_guides=args.max_guides)
     if lora_dir is not None:
         lora_dir.cleanup()  # the adapters are in HBM now
     t_load = time.perf_counter() - t0
@@ -114,6 +119,14 @@ def main():
     sp = SamplingParams(max_tokens=args.output_len, temperature=args.temperature, top_p=args.top_p, top_k=args.top_k,
                         min_p=args.min_p, ignore_eos=True, presence_penalty=args.presence_penalty,
                         frequency_penalty=args.frequency_penalty, repetition_penalty=args.repetition_penalty)
+
+    if args.guided:
+        from dstack_amd.serving import guided
+        from dstack_amd.serving.tokenizer import load_tokenizer
+
+        if not eng.eos_token_ids:
+            eng.eos_token_ids = tuple(load_tokenizer(m.spec.path, vocab).eos_token_ids)
+        sp.ignore_eos, sp.guide = False, guided.compile_json_object()
 
     shared = rng.integers(10, vocab - 10, size=args.shared_prefix_len).tolist() if args.shared_prefix_len else []
 
@@ -165,6 +178,8 @@ def main():
         "prefill_tokens_per_s": round(st["prefill_tokens"] / st["prefill_s"], 1) if st["prefill_s"] else None,
         # prompt tokens admitted (computed + served from the prefix cache) per second of prefill steps
         "prompt_tokens_per_prefill_s": round((st["prefill_tokens"] + hits) / st["prefill_s"], 1) if st["prefill_s"] else None,
+        "guided": args.guided, "max_guides": eng.max_guides,
+        "finished_stop": sum(r.finish_reason == "stop" for r in reqs),
         "num_loras": args.num_loras, "lora_rank": args.lora_rank if args.num_loras else None,
         "lora_idle": args.lora_idle, "lora_requests": sum(eng.lora_requests.values()),
         "prefix_caching": args.enable_prefix_caching, "shared_prefix_len": args.shared_prefix_len,

@@ -49,6 +49,9 @@ int dsa_logit_bias_max();
 hipError_t dsa_apply_penalties(void*, long, int, int, const int*, int, const int*, const float*, const float*,
                                const float*, const float*, const int*, const float*, const int*, hipStream_t);
 hipError_t dsa_penalties_update(int*, int, int, const int*, const int*, int, hipStream_t);
+int dsa_guide_max_states();
+hipError_t dsa_apply_guide(void*, long, int, int, const int*, const int*, int, const void*, const void*, const int*, int,
+                           const void*, int, const int*, int, const int*, hipStream_t);
 bool dsa_lora_shrink_supported(int, int, int, int);
 bool dsa_lora_expand_supported(int, int, int, int, int);
 hipError_t dsa_lora_shrink(const void*, long, const void*, const int*, float*, int, int, int, int, hipStream_t);
@@ -1164,6 +1167,44 @@ void penalties_update(torch::Tensor state, torch::Tensor slot, torch::Tensor tok
         "penalties_update");
 }
 
+// --- structured outputs (guide.hip): every tensor is caller-owned, nothing is allocated or read back ---
+int64_t guide_max_states() { return dsa_guide_max_states(); }
+
+// logits masked in place for the rows with guide >= 0: trans (u)int16 [G, states, 256], accept uint8
+// [G, states], tok_off int32 [ntok + 1] into the uint8 blob tok_bytes, eos_ids int32 [>= 1], n_eos int32 [1]
+void apply_guide(torch::Tensor logits, torch::Tensor guide, torch::Tensor state, torch::Tensor trans,
+                 torch::Tensor accept, torch::Tensor tok_off, torch::Tensor tok_bytes, torch::Tensor eos_ids,
+                 torch::Tensor n_eos) {
+  check_logits(logits);
+  const int64_t rows = logits.size(0), V = logits.size(1), S = dsa_guide_max_states();
+  check_i32_rows(guide, rows, "guide");
+  check_i32_rows(state, rows, "state");
+  TORCH_CHECK(trans.is_cuda() && trans.is_contiguous() && trans.element_size() == 2 &&
+                  (trans.scalar_type() == torch::kInt16 || trans.scalar_type() == torch::kUInt16) &&
+                  trans.dim() == 3 && trans.size(0) >= 1 && trans.size(1) == S && trans.size(2) == 256,
+              "trans must be a contiguous 16-bit integer ROCm tensor [G, ", S, ", 256]");
+  const int64_t G = trans.size(0);
+  TORCH_CHECK(accept.is_cuda() && accept.is_contiguous() && accept.scalar_type() == torch::kUInt8 &&
+                  accept.dim() == 2 && accept.size(0) == G && accept.size(1) == S,
+              "accept must be a contiguous uint8 ROCm tensor [G, ", S, "]");
+  check_i32(tok_off, "tok_off");
+  TORCH_CHECK(tok_off.dim() == 1 && tok_off.numel() >= 1 && tok_off.numel() <= (int64_t)1 << 30,
+              "tok_off must be int32 [tokens + 1]");
+  TORCH_CHECK(tok_bytes.is_cuda() && tok_bytes.is_contiguous() && tok_bytes.scalar_type() == torch::kUInt8 &&
+                  tok_bytes.dim() == 1 && tok_bytes.numel() < (int64_t)1 << 31,
+              "tok_bytes must be a contiguous uint8 ROCm tensor");
+  check_i32(eos_ids, "eos_ids");
+  TORCH_CHECK(eos_ids.dim() == 1 && eos_ids.numel() >= 1, "eos_ids must be int32 [>= 1]");
+  check_i32_rows(n_eos, 1, "n_eos");
+  TORCH_CHECK(rows <= 65535, "apply_guide: at most 65535 rows");
+  check(dsa_apply_guide(logits.data_ptr(), logits.stride(0), (int)rows, (int)V, guide.data_ptr<int>(),
+                        state.data_ptr<int>(), (int)G, trans.data_ptr(), accept.data_ptr(), tok_off.data_ptr<int>(),
+                        (int)tok_off.numel() - 1, tok_bytes.data_ptr(), (int)tok_bytes.numel(),
+                        eos_ids.data_ptr<int>(), (int)std::min<int64_t>(eos_ids.numel(), 1 << 20),
+                        n_eos.data_ptr<int>(), stream()),
+        "apply_guide");
+}
+
 // --- batched multi-LoRA (lora.hip): every tensor is caller-owned, nothing is allocated or read back ---
 bool lora_shrink_supported(int64_t T, int64_t S, int64_t L, int64_t K) {
   return dsa_lora_shrink_supported((int)T, (int)S, (int)L, (int)K);
@@ -1309,6 +1350,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("top_logprobs_max", &dsa_top_logprobs_max);
   m.def("apply_penalties", &apply_penalties);
   m.def("penalties_update", &penalties_update);
+  m.def("guide_max_states", &guide_max_states);
+  m.def("apply_guide", &apply_guide);
   m.def("logit_bias_max", &dsa_logit_bias_max);
   m.def("lora_shrink", &lora_shrink);
   m.def("lora_expand", &lora_expand);

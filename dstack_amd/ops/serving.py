@@ -594,6 +594,81 @@ def penalties_update(state: torch.Tensor, slot: torch.Tensor, tokens: torch.Tens
 
 
 # ----------------------------------------------------------------------------------------------
+# Structured outputs (the token mask of a byte-level DFA): csrc/guide.hip
+# ----------------------------------------------------------------------------------------------
+GUIDE_MAX_STATES = 4096  # rows of one grammar's transition table
+GUIDE_EOS_MAX = 8  # EOS ids the mask looks at
+
+
+def _guide_keep_ref(trans, accept_s: bool, s: int, off: list, blob: list, V: int, eos) -> torch.Tensor:
+    """bool [V]: the tokens the grammar table ``trans`` (numpy uint16 [S, 256]) keeps in state ``s``."""
+    keep = [False] * V
+    for v in range(min(V, len(off) - 1)):
+        b0, b1 = off[v], off[v + 1]
+        if b0 < 0 or b1 <= b0 or b1 > len(blob):
+            continue
+        cur = s
+        for i in range(b0, b1):
+            cur = int(trans[cur, blob[i]])
+            if cur >= GUIDE_MAX_STATES:
+                cur = 0
+            if cur == 0:
+                break
+        keep[v] = cur != 0
+    if accept_s:
+        for e in eos:
+            if 0 <= e < V:
+                keep[e] = True
+    return torch.tensor(keep, dtype=torch.bool)
+
+
+def apply_guide_ref(logits, guide, state, trans, accept, tok_off, tok_bytes, eos_ids, n_eos) -> torch.Tensor:
+    """Reference of :func:`apply_guide`: a plain loop over rows, tokens and bytes on the CPU.  Returns
+    a new tensor like ``logits`` (rows with ``guide < 0`` or an out-of-range guide / state are copies)."""
+    import numpy as np
+
+    out = logits.detach().cpu().clone()
+    t16 = trans.detach().cpu()
+    t16 = t16.view(torch.int16) if t16.dtype == torch.uint16 else t16
+    acc, off, blob = accept.cpu(), tok_off.cpu().tolist(), tok_bytes.cpu().tolist()
+    ne = max(0, min(int(n_eos.reshape(-1)[0]) if torch.is_tensor(n_eos) else int(n_eos), eos_ids.numel(), GUIDE_EOS_MAX))
+    eos = eos_ids.cpu().tolist()[:ne]
+    V = out.shape[1]
+    for r, (g, s) in enumerate(zip(guide.cpu().tolist(), state.cpu().tolist())):
+        if not (0 <= g < t16.shape[0] and 0 <= s < GUIDE_MAX_STATES):
+            continue
+        keep = _guide_keep_ref(t16[g].numpy().view(np.uint16), bool(acc[g, s]), s, off, blob, V, eos)
+        out[r, ~keep] = float("-inf")
+    return out.to(logits.device)
+
+
+def apply_guide(logits: torch.Tensor, guide: torch.Tensor, state: torch.Tensor, trans: torch.Tensor,
+                accept: torch.Tensor, tok_off: torch.Tensor, tok_bytes: torch.Tensor, eos_ids: torch.Tensor,
+                n_eos: torch.Tensor) -> torch.Tensor:
+    """Mask, in place, the logits of every row r with ``guide[r] >= 0`` (int32; -1: the row asks for
+    nothing and is not written) by the byte-level DFA ``trans[guide[r]]`` (16-bit [G, 4096, 256],
+    state 0 dead) / ``accept[guide[r]]`` (uint8 [G, 4096]) in state ``state[r]``.  Token v is kept iff
+
+    * v is one of the first ``n_eos`` (int32 [1], at most 8) ids of ``eos_ids`` and the state accepts, or
+    * v has at least one byte (``tok_bytes[tok_off[v] : tok_off[v + 1]]``; ids from ``len(tok_off) - 1``
+      on have none) and walking its bytes from the state never reaches state 0.
+
+    Every other logit becomes -inf; kept logits keep their bits.  A guide or state out of range leaves
+    the row untouched.  On ROCm tensors nothing is allocated or read back (hipGraph-capturable).
+    Returns ``logits``."""
+    if _ext.use_hip(logits):
+        if trans.dtype == torch.uint16:
+            trans = trans.view(torch.int16)
+        _ext.require().apply_guide(logits, guide, state, trans, accept, tok_off, tok_bytes, eos_ids, n_eos)
+        return logits
+    rows = guide >= 0
+    if bool(rows.any()):
+        ref = apply_guide_ref(logits, guide, state, trans, accept, tok_off, tok_bytes, eos_ids, n_eos)
+        logits[rows] = ref[rows]
+    return logits
+
+
+# ----------------------------------------------------------------------------------------------
 # Batched multi-LoRA projections: csrc/lora.hip
 # ----------------------------------------------------------------------------------------------
 LORA_RANKS = (8, 16, 32, 64)  # padded ranks the kernels take

@@ -45,6 +45,9 @@ def main(argv=None):
     ap.add_argument("--ngram-min", type=int, default=1, help="shortest suffix the proposal matches")
     ap.add_argument("--speculative-max-batch", type=int, default=32,
                     help="decode steps with more running sequences than this run without drafts")
+    ap.add_argument("--max-guides", type=int, default=16, metavar="N",
+                    help="structured outputs (response_format, guided_json / _regex / _choice): grammars resident "
+                         "on the device at once (2 MiB each); 0 allocates nothing and refuses such requests")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(levelname)s %(message)s")
     log = logging.getLogger("dstack_amd.serving")
@@ -70,7 +73,8 @@ def main(argv=None):
                                kv_cache_dtype=args.kv_cache_dtype, enable_prefix_caching=args.enable_prefix_caching,
                                lora_modules=lora_modules or None, max_lora_rank=args.max_lora_rank,
                                speculative_ngram=args.speculative_ngram, ngram_max=args.ngram_max,
-                               ngram_min=args.ngram_min, speculative_max_batch=args.speculative_max_batch)
+                               ngram_min=args.ngram_min, speculative_max_batch=args.speculative_max_batch,
+                               max_guides=args.max_guides)
     eng.capture_graphs()
     m = eng.model
     log.info("model %s: %.1f GB weights, %d KV pages (%d tokens), max_model_len %d, %d decode graphs, ready in %.1fs",
@@ -78,6 +82,8 @@ def main(argv=None):
              time.time() - t0)
     if lora_modules:
         log.info("LoRA adapters: %s (rank padded to %d)", ", ".join(lora_modules), m.lora_rank)
+    if eng.guide_error and args.max_guides:
+        log.warning("%s", eng.guide_error)
     name = args.served_model_name or os.path.basename(os.path.normpath(args.model))
     uvicorn.run(create_app(eng, name), host=args.host, port=args.port, log_level="info")
 

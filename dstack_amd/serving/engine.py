@@ -52,6 +52,8 @@ class SamplingParams:
     frequency_penalty: float = 0.0  # times the token's count among the generated tokens; [-2, 2]
     repetition_penalty: float = 1.0  # divides (x > 0) or multiplies the logits of prompt and generated tokens; (0, 2]
     logit_bias: dict | None = None  # {token id: bias in [-100, 100]}, at most LOGIT_BIAS_MAX entries
+    # structured output: a compiled grammar (serving.guided.Guide); every token's bytes must keep its DFA alive
+    guide: object = None
 
     @property
     def wants_penalties(self) -> bool:
@@ -93,6 +95,7 @@ class Request:
     logit_bias: dict = field(default_factory=dict)  # params.logit_bias, validated: {int token id: float}
     lora: str | None = None  # the adapter the request asked for (add_request(..., lora=name))
     lora_slot: int = -1  # its slot in the model's adapter stacks; -1: the base model
+    guide_state: int = 1  # the DFA state of params.guide after the tokens emitted so far (1: the start)
 
     @property
     def all_ids(self):
@@ -116,8 +119,12 @@ class LLMEngine:
                  num_pages: int | None = None, use_graphs: bool | None = None, gpu_memory_utilization: float = 0.90,
                  eos_token_ids=(), enable_prefix_caching: bool = False, lora_modules: dict | None = None,
                  max_lora_rank: int = 64, speculative_ngram: int = 0, ngram_max: int = 3, ngram_min: int = 1,
-                 speculative_max_batch: int = 32):
+                 speculative_max_batch: int = 32, max_guides: int = 16, token_bytes=None):
         from dstack_amd.serving import _native
+
+        if isinstance(max_guides, bool) or not isinstance(max_guides, int) or max_guides < 0:
+            raise ValueError(f"max_guides must be an integer >= 0, got {max_guides!r}")
+        self.max_guides, self._token_bytes = max_guides, token_bytes
 
         if enable_prefix_caching and model.tp > 1:
             raise ValueError("prefix caching is not supported with tensor parallel yet")
@@ -183,6 +190,8 @@ class LLMEngine:
             self.verify_buckets = sorted(r for r in want if r is not None)
         self._alloc_static()
         self.stats = dict(prefill_tokens=0, decode_tokens=0, steps=0, preemptions=0, prefill_s=0.0, decode_s=0.0)
+        if self.max_guides:
+            self.stats.update(guided_requests=0)
         if self.spec_k:
             self.stats.update(spec_steps=0, spec_drafted=0, spec_accepted=0)
         if self.prefix_caching:
@@ -250,6 +259,7 @@ class LLMEngine:
         self._reset_penalty_rows(N)
         self._pen_free = list(range(B - 1, -1, -1))
         self._pen_slots: dict[int, int] = {}  # request id -> slot
+        self._alloc_guides(N)
         # LoRA: every row's adapter slot (padding rows and base-model rows: -1)
         self.s_lora_idx = torch.full((B,), -1, **i32)
         self._lora_rows_set = 0  # leading rows of s_lora_idx that may hold a slot
@@ -258,6 +268,52 @@ class LLMEngine:
             self.s_qlens = torch.zeros(B, **i32)  # rows in use per sequence of a verify step
             self._vws = {r: sops.VerifyWorkspace(r, self.spec_T, self.model.H, self.model.KVH, W, dev)
                          for r in self.verify_buckets}
+
+    def _alloc_guides(self, N: int):
+        """Structured outputs: a pool of ``max_guides`` grammars (16-bit transitions [G, 4096, 256] and
+        uint8 acceptance [G, 4096]: 2 MiB + 4 KiB each), the tokenizer's byte table, the EOS ids and
+        per-row (grammar slot, DFA state); padding rows and rows that ask for nothing: slot -1.
+        Allocated after the KV cache is sized; only the leader samples, so only the leader holds it."""
+        self.guide_error = None  # why guided requests are refused (None: they are accepted)
+        self._guide_slot: dict[str, int] = {}  # content hash -> pool slot (resident grammars)
+        self._guide_refs: dict[str, int] = {}  # content hash -> live requests that hold it
+        self._guide_lru: dict[str, None] = {}  # resident, unreferenced hashes, least recently used first
+        self._guide_free: list[int] = []
+        self._guide_held: dict[int, str] = {}  # request id -> content hash
+        self._guide_rows_set = 0
+        self._eos_staged = None
+        if not self.max_guides:
+            self.guide_error = "structured outputs are disabled (max_guides = 0)"
+            return
+        if not self.leader:
+            self.max_guides = 0
+            return
+        from dstack_amd.serving import guided
+        from dstack_amd.serving.tokenizer import load_tokenizer
+
+        dev, V, G = self.device, self.model.cfg.vocab_size, self.max_guides
+        try:
+            table = self._token_bytes
+            if table is None:
+                table = load_tokenizer(self.model.spec.path, V).token_bytes()
+            off, blob = guided.pack_token_bytes(table, V)
+        except Exception as e:  # noqa: BLE001 - an unsupported tokenizer refuses guided requests, nothing else
+            self.guide_error, self.max_guides = f"structured outputs are not available: {e}", 0
+            return
+        self.token_bytes = [bytes(b) for b in table][:V] + [b""] * max(0, V - len(table))
+        self.g_trans = torch.zeros(G, sops.GUIDE_MAX_STATES, 256, dtype=torch.int16, device=dev)
+        self.g_accept = torch.zeros(G, sops.GUIDE_MAX_STATES, dtype=torch.uint8, device=dev)
+        self.g_tok_off = torch.from_numpy(off).to(dev)
+        self.g_tok_bytes = torch.from_numpy(blob).to(dev)
+        self.g_eos = torch.full((sops.GUIDE_EOS_MAX,), -1, dtype=torch.int32, device=dev)
+        self.g_n_eos = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.s_guide = torch.full((N,), -1, dtype=torch.int32, device=dev)
+        self.s_guide_state = torch.zeros(N, dtype=torch.int32, device=dev)
+        self._guide_free = list(range(G - 1, -1, -1))
+
+    def _apply_guide(self, logits, guide, state):
+        return sops.apply_guide(logits, guide, state, self.g_trans, self.g_accept, self.g_tok_off, self.g_tok_bytes,
+                                self.g_eos, self.g_n_eos)
 
     def _reset_penalty_rows(self, m: int):
         self.s_pen_slot[:m].fill_(-1)
@@ -273,6 +329,8 @@ class LLMEngine:
         logits = self.model.decode(self.s_tokens[:b], self.s_pos[:b], self.s_slots[:b], self.s_tables[:b],
                                    self.s_ctx[:b], ws=self._ws[b], **(dict(lora_idx=self.s_lora_idx[:b]) if lora else {}))
         self._apply_penalties(logits, self.s_pen_slot[:b], self.s_pen[:, :b])
+        if self.max_guides:
+            self._apply_guide(logits, self.s_guide[:b], self.s_guide_state[:b])
         sops.sample_filtered(logits, self.s_temps[:b], self.s_seeds[:b], self.s_steps[:b], self.s_top_k[:b],
                              self.s_top_p[:b], self.s_min_p[:b], self.s_out_tok[:b], self.s_out_lp[:b],
                              top_n=self.s_top_n[:b], top_ids=self.s_top_ids[:b], top_lps=self.s_top_lps[:b],
@@ -290,6 +348,8 @@ class LLMEngine:
         logits = self.model.verify(self.s_tokens[:R], self.s_pos[:R], self.s_slots[:R], self.s_tables[:nb],
                                    self.s_ctx[:nb], self.s_qlens[:nb], self.spec_T, ws=self._vws[R])
         self._apply_penalties(logits, self.s_pen_slot[:R], self.s_pen[:, :R])
+        if self.max_guides:
+            self._apply_guide(logits, self.s_guide[:R], self.s_guide_state[:R])
         sops.sample_filtered(logits, self.s_temps[:R], self.s_seeds[:R], self.s_steps[:R], self.s_top_k[:R],
                              self.s_top_p[:R], self.s_min_p[:R], self.s_out_tok[:R], self.s_out_lp[:R],
                              top_n=self.s_top_n[:R], top_ids=self.s_top_ids[:R], top_lps=self.s_top_lps[:R],
@@ -310,6 +370,9 @@ class LLMEngine:
         self.s_top_n.zero_()
         self._filter_rows_set = 0
         self._reset_penalty_rows(self.rows_max)
+        if self.max_guides:
+            self.s_guide.fill_(-1)
+            self._guide_rows_set = 0
         self.s_lora_idx.fill_(-1)
         self._lora_rows_set = 0
         if self.spec_k:
@@ -362,6 +425,8 @@ class LLMEngine:
         if not 0 <= params.top_logprobs <= sops.TOP_LOGPROBS_MAX:
             raise ValueError(f"top_logprobs must be in [0, {sops.TOP_LOGPROBS_MAX}], got {params.top_logprobs}")
         logit_bias = check_penalties(params, vocab)
+        if params.guide is not None:
+            self._check_guide(params)
         rid = next(self._ids)
         seed = params.seed if params.seed is not None else (rid * 7919 + 17)
         req = Request(rid, list(prompt_ids), params, on_event=on_event, seed=int(seed), logit_bias=logit_bias,
@@ -369,6 +434,8 @@ class LLMEngine:
         with self._lock:
             if lora is not None:
                 self.lora_requests[lora] += 1
+            if params.guide is not None:
+                self.stats["guided_requests"] += 1
             self.requests[rid] = req
             self._pending.append(req)
         self._wake.set()
@@ -391,8 +458,12 @@ class LLMEngine:
         with self._lock:
             pending, self._pending = self._pending, []
             aborted, self._aborted = getattr(self, "_aborted", set()), set()
+        held = []
         for req in pending:
             if req.finished:
+                continue
+            if req.params.guide is not None and not self._take_guide(req):
+                held.append(req)  # every grammar slot is referenced: wait for one (never dropped)
                 continue
             if self.prefix_caching:
                 # (the salt keeps the cached K/V of one adapter from serving another's prompt)
@@ -400,9 +471,13 @@ class LLMEngine:
                                np.asarray(req.prompt_ids, dtype=np.int32), salt=req.lora_slot + 1)
             else:
                 self.sched.add(req.id, len(req.prompt_ids), len(req.prompt_ids) + req.params.max_tokens)
+        if held:
+            with self._lock:
+                self._pending[:0] = held
         for rid in aborted:
             self.sched.finish(rid)
             self._release_penalty_slot(rid)
+            self._release_guide(rid)
             self._emit(self.requests.pop(rid, None), None, True)
 
     def _emit(self, req, token, finished):
@@ -491,6 +566,14 @@ class LLMEngine:
                 else:
                     self.sched.append(req.id)
                 emitted += 1
+                if req.params.guide is not None:
+                    # the host is the single source of truth of the DFA state
+                    if tok not in self.eos_token_ids:
+                        req.guide_state = self._guide_advance(req, tok)
+                    elif not req.params.guide.accept[req.guide_state]:
+                        raise RuntimeError(f"structured output: the mask let EOS {tok} through in state "
+                                           f"{req.guide_state}, where the grammar of request {req.id} does not "
+                                           "accept (a bug, not a request error)")
                 reason = None
                 if len(req.output_ids) >= req.params.max_tokens:
                     reason = "length"
@@ -502,6 +585,7 @@ class LLMEngine:
                     req.finished, req.finish_reason, req.finished_at = True, reason, now
                     self.sched.finish(req.id)
                     self._release_penalty_slot(req.id)
+                    self._release_guide(req.id)
                 self._emit(req, tok, req.finished)
                 if req.finished:  # the tokens after a finishing one are dropped
                     self.requests.pop(req.id, None)
@@ -595,6 +679,96 @@ class LLMEngine:
             self._lora_rows_set = 0
         return False
 
+    # ------------------------------------------------------------------------------------------
+    # structured outputs
+    # ------------------------------------------------------------------------------------------
+    def _check_guide(self, params):
+        from dstack_amd.serving.guided import Guide
+
+        if self.guide_error:
+            raise ValueError(self.guide_error)
+        g = params.guide
+        if not isinstance(g, Guide) or g.states > sops.GUIDE_MAX_STATES:
+            raise ValueError("guide must be a compiled grammar (dstack_amd.serving.guided)")
+        if params.ignore_eos:
+            raise ValueError("ignore_eos cannot be combined with a structured output (guide): the grammar ends "
+                             "the output with EOS")
+        if not self.eos_token_ids:
+            raise ValueError("a structured output needs an EOS token id to end with; the engine has none")
+
+    def _take_guide(self, req) -> bool:
+        """Reference the request's grammar, uploading it when it is not resident (into a free slot or
+        over the least recently used unreferenced one).  False: every slot is referenced."""
+        g = req.params.guide
+        if req.id in self._guide_held:
+            return True
+        if g.key not in self._guide_slot:
+            if self._guide_free:
+                slot = self._guide_free.pop()
+            elif self._guide_lru:
+                old = next(iter(self._guide_lru))
+                del self._guide_lru[old]
+                slot = self._guide_slot.pop(old)
+            else:
+                return False
+            S = g.states
+            self.g_trans[slot].zero_()
+            self.g_accept[slot].zero_()
+            self.g_trans[slot, :S].copy_(torch.from_numpy(g.trans.view(np.int16)))
+            self.g_accept[slot, :S].copy_(torch.from_numpy(g.accept))
+            self._guide_slot[g.key] = slot
+        self._guide_lru.pop(g.key, None)
+        self._guide_refs[g.key] = self._guide_refs.get(g.key, 0) + 1
+        self._guide_held[req.id] = g.key
+        return True
+
+    def _release_guide(self, rid: int):
+        key = self._guide_held.pop(rid, None)
+        if key is None:
+            return
+        self._guide_refs[key] -= 1
+        if self._guide_refs[key] == 0:
+            del self._guide_refs[key]
+            self._guide_lru[key] = None  # stays resident until its slot is needed
+
+    def _guide_advance(self, req, tok: int, state: int | None = None) -> int:
+        from dstack_amd.serving.guided import advance
+
+        s = advance(req.params.guide, req.guide_state if state is None else state, self.token_bytes[tok])
+        if state is None and (s == 0 or not self.token_bytes[tok]):
+            raise RuntimeError(f"structured output: the mask let token {tok} through, which the grammar of request "
+                               f"{req.id} refuses in state {req.guide_state} (a bug, not a request error)")
+        return s
+
+    def _guide_rows(self, rows):
+        """slot and state int32 tensors of ``rows``: per row ``(request, state)`` or None (nothing asked)."""
+        slot = [self._guide_slot[self._guide_held[r[0].id]] if r is not None else -1 for r in rows]
+        state = [r[1] if r is not None else 0 for r in rows]
+        return torch.tensor(slot, dtype=torch.int32), torch.tensor(state, dtype=torch.int32)
+
+    def _stage_eos(self):
+        if self._eos_staged != self.eos_token_ids:
+            ids = [int(e) for e in self.eos_token_ids][: sops.GUIDE_EOS_MAX]
+            self.g_eos.copy_(torch.tensor(ids + [-1] * (sops.GUIDE_EOS_MAX - len(ids)), dtype=torch.int32))
+            self.g_n_eos.fill_(len(ids))
+            self._eos_staged = self.eos_token_ids
+
+    def _stage_guides(self, rows, b: int):
+        """Stage grammar slots and DFA states into the static buffers, as ``_stage_penalties`` does:
+        steps where no row is guided (the common case) copy nothing."""
+        if not self.max_guides:
+            return
+        if any(r is not None for r in rows):
+            self._stage_eos()
+            m = max(b, self._guide_rows_set)
+            slot, state = self._guide_rows(list(rows) + [None] * (m - len(rows)))
+            self.s_guide[:m].copy_(slot, non_blocking=True)
+            self.s_guide_state[:m].copy_(state, non_blocking=True)
+            self._guide_rows_set = len(rows)
+        elif self._guide_rows_set:
+            self.s_guide[: self._guide_rows_set].fill_(-1)
+            self._guide_rows_set = 0
+
     @staticmethod
     def _tops(reqs, ids, lps):
         """The top-N outputs on the host, copied only in steps where some request asked for them."""
@@ -614,6 +788,10 @@ class LLMEngine:
         if any(r.id in self._pen_slots for r in reqs):
             slot, pen = (t.to(self.device) for t in self._penalty_rows(reqs))
             self._apply_penalties(logits, slot, pen)
+        if self.max_guides and any(r.params.guide is not None for r in reqs):
+            self._stage_eos()
+            gslot, gstate = self._guide_rows([(r, r.guide_state) if r.params.guide is not None else None for r in reqs])
+            self._apply_guide(logits, gslot.to(self.device), gstate.to(self.device))
         tok, lp, ids, tlp = sops.sample_filtered(logits, temps, seeds, steps, top_k, top_p, min_p, top_n=top_n)
         if slot is not None:
             sops.penalties_update(self.p_state, slot, tok)
@@ -637,6 +815,7 @@ class LLMEngine:
             self.s_steps[:n].copy_(steps, non_blocking=True)
             self._stage_filters(reqs, b)
             self._stage_penalties(reqs, b)
+            self._stage_guides([(r, r.guide_state) if r.params.guide is not None else None for r in reqs], b)
             lora = self._stage_lora(reqs, b)
             if b > n:
                 self.s_slots[n:b].fill_(-1)
@@ -665,7 +844,15 @@ class LLMEngine:
         counts depend on every earlier token)."""
         if grant <= 0 or req.params.wants_penalties:
             return []
-        return self._propose(np.asarray(req.all_ids, dtype=np.int32), grant, self.ngram_max, self.ngram_min).tolist()
+        d = self._propose(np.asarray(req.all_ids, dtype=np.int32), grant, self.ngram_max, self.ngram_min).tolist()
+        if req.params.guide is not None:
+            # walk the drafts through the grammar and cut them at the first token it refuses
+            s = req.guide_state
+            for j, t in enumerate(d):
+                s = self._guide_advance(req, t, s) if self.token_bytes[t] else 0
+                if s == 0:
+                    return d[:j]
+        return d
 
     def _verify(self, plan, reqs, drafts):
         """One verify step: row ``b*T`` carries sequence b's last token and rows ``b*T + 1 ..`` its
@@ -693,6 +880,16 @@ class LLMEngine:
         # per-row sampler inputs: a sequence's filters on all of its rows, its penalty slot on its first
         row_reqs = [r for r in reqs for _ in range(T)]
         pen_reqs = [r if j == 0 else None for r in reqs for j in range(T)]
+        guide_rows = []  # row j of a guided sequence: the state after its drafts [:j]
+        for r, d in zip(reqs, drafts):
+            if r.params.guide is None:
+                guide_rows += [None] * T
+                continue
+            s = r.guide_state
+            for j in range(T):
+                guide_rows.append((r, s) if j <= len(d) else None)
+                if j < len(d):
+                    s = self._guide_advance(r, d[j], s)
         nbf = torch.from_numpy
         with torch.no_grad():
             self.s_tokens[:R].copy_(nbf(tokens), non_blocking=True)
@@ -706,6 +903,7 @@ class LLMEngine:
             self.s_steps[:R].copy_(nbf(steps), non_blocking=True)
             self._stage_filters(row_reqs, R)
             self._stage_penalties(pen_reqs, R)
+            self._stage_guides(guide_rows, R)
             if ("verify", R) in self._graphs:
                 self._graphs["verify", R].replay()
             else:
@@ -827,12 +1025,15 @@ class LLMEngine:
                 for r in victims:
                     self.sched.finish(r.id)
                     self._release_penalty_slot(r.id)
+                    self._release_guide(r.id)
                     r.finished, r.finish_reason = True, f"error: {e}"
                     self._emit(r, None, True)
 
     def metrics(self) -> dict:
         if self.prefix_caching:
             self.stats["prefix_cached_pages"] = self.sched.cached_pages
+        if self.max_guides:
+            self.stats["guided_grammars_resident"] = len(self._guide_slot)
         return dict(self.stats, running=self.sched.num_running, waiting=self.sched.num_waiting + len(self._pending),
                     kv_pages_free=self.sched.free_pages, kv_pages_total=self.sched.num_pages,
                     kv_usage=1.0 - self.sched.free_pages / max(1, self.sched.num_pages))

@@ -15,7 +15,9 @@ thread feeds through ``loop.call_soon_threadsafe``.
 from __future__ import annotations
 
 import asyncio
+import collections
 import json
+import threading
 import time
 import uuid
 
@@ -24,7 +26,11 @@ from fastapi.responses import JSONResponse, PlainTextResponse, StreamingResponse
 
 from dstack_amd.ops.serving import TOP_LOGPROBS_MAX
 from dstack_amd.serving.engine import LLMEngine, SamplingParams, check_penalties
+from dstack_amd.serving import guided
 from dstack_amd.serving.tokenizer import load_tokenizer
+
+GUIDE_CACHE_SIZE = 64  # compiled grammars the server keeps, least recently used out first
+GUIDE_FIELDS = ("response_format", "guided_json", "guided_regex", "guided_choice")
 
 
 class _Stream:
@@ -68,7 +74,10 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
             u["prompt_tokens_details"] = {"cached_tokens": sum(r.cached_tokens for r in reqs)}
         return u
 
-    state = dict(requests=0, ttft_sum=0.0, ttft_n=0, gen_tokens=0, prompt_tokens=0, started=time.time())
+    state = dict(requests=0, ttft_sum=0.0, ttft_n=0, gen_tokens=0, prompt_tokens=0, started=time.time(),
+                 guide_compile_s=0.0)
+    guide_cache: collections.OrderedDict = collections.OrderedDict()  # canonical JSON of the constraint -> Guide
+    guide_lock = threading.Lock()
 
     from contextlib import asynccontextmanager
 
@@ -116,7 +125,78 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
             raise _bad(f"{'top_logprobs' if chat else 'logprobs'} must be between 0 and {TOP_LOGPROBS_MAX}")
         return n
 
-    def _params(body: dict, prompt_len: int, default_max: int, chat: bool = False) -> SamplingParams:
+    def _constraint(body: dict):
+        """``(field, kind, value)`` of the request's structured-output constraint, or None.  At most
+        one of ``response_format`` (other than ``text``) and ``guided_json / _regex / _choice``."""
+        given = [f for f in GUIDE_FIELDS if body.get(f) is not None]
+        rf = body.get("response_format")
+        if rf is not None:
+            if not isinstance(rf, dict) or rf.get("type") not in ("text", "json_object", "json_schema"):
+                raise _bad("response_format.type must be one of text, json_object, json_schema")
+            if rf["type"] == "text":
+                given.remove("response_format")
+        if len(given) > 1:
+            raise _bad(f"at most one structured-output field may be given, got {' and '.join(given)}")
+        if not given:
+            return None
+        field = given[0]
+        if field == "response_format":
+            if rf["type"] == "json_object":
+                return field, "json_object", None
+            js = rf.get("json_schema")
+            if not isinstance(js, dict) or not isinstance(js.get("schema"), dict):
+                raise _bad("response_format.json_schema.schema must be a JSON schema object")
+            return field, "json", js["schema"]
+        return field, field[len("guided_"):], body[field]
+
+    def _compile_guide(field: str, kind: str, value):
+        """The compiled grammar of a constraint, from the cache or compiled here (the calling thread is
+        a worker of the request handler, never the engine loop)."""
+        try:
+            key = json.dumps([kind, value], sort_keys=True, separators=(",", ":"))
+        except (TypeError, ValueError):
+            raise ValueError(f"{field} is not JSON-serialisable") from None
+        with guide_lock:
+            g = guide_cache.get(key)
+            if g is not None:
+                guide_cache.move_to_end(key)
+        if g is None:
+            t0 = time.perf_counter()
+            try:
+                if kind == "json_object":
+                    g = guided.compile_json_object()
+                elif kind == "json":
+                    g = guided.compile_json_schema(value)
+                elif kind == "regex":
+                    g = guided.compile_regex(value)
+                else:
+                    g = guided.compile_choice(value)
+            except ValueError as e:
+                g = e  # a refusal is remembered too: asking again must not compile again
+            with guide_lock:
+                state["guide_compile_s"] += time.perf_counter() - t0
+                guide_cache[key] = g
+                while len(guide_cache) > GUIDE_CACHE_SIZE:
+                    guide_cache.popitem(last=False)
+        if isinstance(g, ValueError):
+            raise ValueError(str(g))
+        return g
+
+    async def _guide(body: dict):
+        """The request's compiled grammar or None; every refusal is a 400 that names the field."""
+        c = _constraint(body)
+        if c is None:
+            return None
+        if engine.guide_error:
+            raise _bad(f"{c[0]}: {engine.guide_error}")
+        if body.get("ignore_eos"):
+            raise _bad(f"ignore_eos cannot be combined with {c[0]}: the grammar ends the output with EOS")
+        try:
+            return await asyncio.get_running_loop().run_in_executor(None, _compile_guide, *c)
+        except ValueError as e:
+            raise _bad(f"{c[0]}: {e}") from e
+
+    def _params(body: dict, prompt_len: int, default_max: int, chat: bool = False, guide=None) -> SamplingParams:
         max_ctx = engine.model.max_model_len
         if prompt_len >= max_ctx:
             raise HTTPException(400, detail={"message": f"prompt has {prompt_len} tokens; this model's maximum "
@@ -136,7 +216,7 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
                             presence_penalty=_num(body, "presence_penalty", float, 0.0),
                             frequency_penalty=_num(body, "frequency_penalty", float, 0.0),
                             repetition_penalty=_num(body, "repetition_penalty", float, 1.0),
-                            logit_bias=body.get("logit_bias"))
+                            logit_bias=body.get("logit_bias"), guide=guide)
         try:
             sp.logit_bias = check_penalties(sp, engine.model.cfg.vocab_size) or None
         except ValueError as e:
@@ -246,6 +326,7 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
         body = await request.json()
         model_name, lora = _check_model(body.get("model"))
         prompts = _prompts(body)
+        guide = await _guide(body)
         n = int(body.get("n") or 1)
         rid = f"cmpl-{uuid.uuid4().hex[:24]}"
         created = int(time.time())
@@ -254,7 +335,7 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
         planned = []
         for p in prompts:
             for k in range(n):
-                params = _params(body, len(p), 16)
+                params = _params(body, len(p), 16, guide=guide)
                 if params.seed is not None and n > 1:
                     params.seed = int(params.seed) + k
                 planned.append((p, params))
@@ -321,7 +402,7 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
         if not isinstance(msgs, list) or not msgs:
             raise HTTPException(400, detail={"message": "messages must be a non-empty list", "type": "invalid_request_error"})
         ids = tok.encode(tok.apply_chat_template(msgs, add_generation_prompt=True), add_bos=True)
-        params = _params(body, len(ids), engine.model.max_model_len - len(ids), chat=True)
+        params = _params(body, len(ids), engine.model.max_model_len - len(ids), chat=True, guide=await _guide(body))
         want_lp = bool(body.get("logprobs"))
         req, q, st = _submit(ids, params, _stop(body), lora)
         rid = f"chatcmpl-{uuid.uuid4().hex[:24]}"
@@ -391,6 +472,13 @@ def create_app(engine: LLMEngine, served_model_name: str, tokenizer=None) -> Fas
               "counter")
             g("dstack_serving_spec_draft_tokens_total", "draft tokens proposed and verified", m["spec_drafted"], "counter")
             g("dstack_serving_spec_accepted_tokens_total", "draft tokens accepted", m["spec_accepted"], "counter")
+        if engine.max_guides:
+            g("dstack_serving_guided_requests_total", "requests with a structured-output constraint",
+              m["guided_requests"], "counter")
+            g("dstack_serving_guided_grammars_resident", "compiled grammars resident on the device",
+              m["guided_grammars_resident"])
+            g("dstack_serving_guided_compile_seconds_total", "time spent compiling grammars",
+              round(state["guide_compile_s"], 6), "counter")
         ttft = state["ttft_sum"] / state["ttft_n"] if state["ttft_n"] else 0.0
         g("dstack_serving_ttft_mean_seconds", "mean time to first token", round(ttft, 6))
         return PlainTextResponse("\n".join(lines) + "\n")

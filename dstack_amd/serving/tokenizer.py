@@ -50,11 +50,37 @@ class ByteTokenizer:
         bs = bytes((i - self.OFFSET) % 256 for i in ids if i >= self.OFFSET)
         return bs.decode("utf-8", errors="replace")
 
+    def token_bytes(self) -> list[bytes]:
+        """The bytes every id contributes to ``decode`` (structured outputs walk them through a DFA)."""
+        return [b"" if i < self.OFFSET else bytes([(i - self.OFFSET) % 256]) for i in range(self.vocab_size)]
+
     def apply_chat_template(self, messages, add_generation_prompt=True) -> str:
         out = ""
         for m in messages:
             out += f"<{m['role']}>{_content(m)}\n"
         return out + ("<assistant>" if add_generation_prompt else "")
+
+
+def _gpt2_unicode_to_byte() -> dict:
+    """Inverse of the GPT-2 byte-to-unicode table the ByteLevel pre-tokenizer / decoder uses."""
+    keep = list(range(ord("!"), ord("~") + 1)) + list(range(0xA1, 0xAC + 1)) + list(range(0xAE, 0xFF + 1))
+    table, n = {}, 0
+    for b in range(256):
+        if b in keep:
+            table[chr(b)] = b
+        else:
+            table[chr(256 + n)] = b
+            n += 1
+    return table
+
+
+def _decoder_kinds(dec) -> set:
+    """The decoder types named in a ``tokenizer.json`` decoder entry (a Sequence is flattened)."""
+    if not isinstance(dec, dict):
+        return set()
+    if dec.get("type") == "Sequence":
+        return set().union(*[_decoder_kinds(d) for d in dec.get("decoders", [])]) if dec.get("decoders") else set()
+    return {dec.get("type")}
 
 
 class HFTokenizer:
@@ -89,6 +115,40 @@ class HFTokenizer:
 
     def decode(self, ids) -> str:
         return self.tok.decode(list(ids), skip_special_tokens=True)
+
+    def token_bytes(self) -> list[bytes]:
+        """The bytes every id contributes to ``decode``, read off the decoder ``tokenizer.json``
+        names: ByteLevel (Llama-3, Qwen2) inverts the GPT-2 byte-to-unicode table; Metaspace /
+        ByteFallback (Llama-2, Mistral) turns ``▁`` into a space and ``<0xNN>`` into that byte.  Added
+        and special tokens are empty.  ValueError for any other decoder."""
+        spec = json.loads(self.tok.to_str())
+        kinds = _decoder_kinds(spec.get("decoder"))
+        vocab = self.tok.get_vocab(with_added_tokens=True)
+        added = {t["id"] for t in spec.get("added_tokens") or []}
+        out = [b""] * (max(vocab.values()) + 1 if vocab else 0)
+        if "ByteLevel" in kinds:
+            inv = _gpt2_unicode_to_byte()
+            for text, i in vocab.items():
+                if i not in added:
+                    try:
+                        out[i] = bytes(inv[c] for c in text)
+                    except KeyError:
+                        raise ValueError(f"token {i} ({text!r}) is not in the ByteLevel alphabet") from None
+        elif kinds & {"Metaspace", "ByteFallback"}:
+            for text, i in vocab.items():
+                if i in added:
+                    continue
+                if len(text) == 6 and text.startswith("<0x") and text.endswith(">") and "ByteFallback" in kinds:
+                    try:
+                        out[i] = bytes([int(text[3:5], 16)])
+                        continue
+                    except ValueError:
+                        pass
+                out[i] = text.replace("▁", " ").encode("utf-8")
+        else:
+            raise ValueError(f"structured outputs need a ByteLevel or Metaspace / ByteFallback tokenizer; this one "
+                             f"decodes with {sorted(k for k in kinds if k) or 'no decoder'}")
+        return out
 
     def apply_chat_template(self, messages, add_generation_prompt=True) -> str:
         if not self.chat_template:
