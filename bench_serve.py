@@ -53,7 +53,7 @@ def main():
     ap.add_argument("--presence-penalty", type=float, default=0.0, help="on every request (0 = off)")
     ap.add_argument("--frequency-penalty", type=float, default=0.0, help="on every request (0 = off)")
     ap.add_argument("--repetition-penalty", type=float, default=1.0, help="on every request (1 = off)")
-    ap.add_argument("--quantization", choices=["fp8", "mxfp4"], default=None)
+    ap.add_argument("--quantization", choices=["fp8", "mxfp4", "awq"], default=None)
     ap.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto")
     ap.add_argument("--enable-prefix-caching", action="store_true",
                     help="reuse cached KV pages of a shared prompt prefix (dstack_amd.serving --enable-prefix-caching)")

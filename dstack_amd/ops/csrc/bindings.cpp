@@ -5,6 +5,8 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
+#include <climits>
+
 extern "C" {
 hipError_t dsa_rmsnorm_fwd(const void*, const void*, const void*, void*, void*, float*, int, int, float,
                            hipStream_t);
@@ -110,6 +112,12 @@ hipError_t dsa_mxfp4_gemm(const void*, const float*, const void*, const void*, v
                           int, hipStream_t);
 hipError_t dsa_mxfp4_quant(const void*, long, void*, void*, int, int, hipStream_t);
 hipError_t dsa_mxfp4_dequant(const void*, const void*, void*, long, int, int, hipStream_t);
+int dsa_w4_gemm_form(int);
+bool dsa_w4_gemm_supported(int, int, int, int);
+int dsa_w4_gemm_split(int, int, int);
+hipError_t dsa_w4_gemm(const void*, const void*, const void*, const void*, void*, float*, int, int, int, int, long, long,
+                       int, hipStream_t);
+hipError_t dsa_w4_dequant(const void*, const void*, const void*, void*, long, int, int, int, hipStream_t);
 }
 
 namespace {
@@ -739,6 +747,64 @@ torch::Tensor mxfp4_dequant(torch::Tensor wc, torch::Tensor wsc, int64_t N, int6
   return out;
 }
 
+// ---- W4A16 weights of AWQ checkpoints (csrc/w4.hip) ----
+void check_w4_stored(const torch::Tensor& wc, const torch::Tensor& wz, const torch::Tensor& wsc, int64_t N, int64_t K,
+                     int64_t g, const char* what) {
+  TORCH_CHECK(g == 32 || g == 64 || g == 128, what, ": group size 32, 64 or 128");
+  TORCH_CHECK(N > 0 && N % 16 == 0 && K > 0 && K % g == 0, what, ": N % 16 == 0, K % g == 0");
+  for (auto* t : {&wc, &wz, &wsc})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() && reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, what,
+                ": stored codes, zeros and scales are contiguous, 16-byte aligned ROCm tensors");
+  TORCH_CHECK(wc.scalar_type() == torch::kUInt8 && wz.scalar_type() == torch::kUInt8 &&
+                  wsc.scalar_type() == torch::kFloat16,
+              what, ": stored codes and zeros are uint8, stored scales fp16");
+  const int64_t Kp = (K + 127) / 128 * 128;  // the stored form pads K to whole K-steps
+  TORCH_CHECK(wc.numel() == N * Kp / 2 && wz.numel() == N * Kp / g && wsc.numel() == N * Kp / g, what,
+              ": stored codes hold N Kp / 2 bytes, stored zeros and scales N Kp / g elements (Kp: K rounded up to 128)");
+}
+
+bool w4_gemm_supported(int64_t M, int64_t N, int64_t K, int64_t g) {
+  return M <= INT_MAX && N <= INT_MAX && K <= INT_MAX && dsa_w4_gemm_supported((int)M, (int)N, (int)K, (int)g);
+}
+
+// y[M][N] = bf16(x W^T) for a decode batch of up to 256 rows: x bf16 [M][K], W the stored W4 weight
+// (ops.serving.w4_shuffle); split-K partials are allocated here, added by a second kernel
+torch::Tensor w4_gemm(torch::Tensor x, torch::Tensor wc, torch::Tensor wz, torch::Tensor wsc, int64_t N, int64_t K,
+                      int64_t g) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 && x.dim() == 2 && x.stride(1) == 1 && x.size(1) == K,
+              "w4_gemm: x is bf16 [M, K] with contiguous rows");
+  TORCH_CHECK(x.stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "w4_gemm: 16-byte aligned activation rows");
+  const int64_t M = x.size(0);
+  TORCH_CHECK(w4_gemm_supported(M, N, K, g),
+              "w4_gemm: 1 <= M <= 256, N % 256 == 0, K % 512 == 0, group size 32, 64 or 128");
+  check_w4_stored(wc, wz, wsc, N, K, g, "w4_gemm");
+  const int S = dsa_w4_gemm_split((int)M, (int)N, (int)K);
+  auto y = torch::empty({M, N}, x.options());
+  torch::Tensor part;
+  if (S > 1) part = torch::empty({S, M, N}, x.options().dtype(torch::kFloat32));
+  check(dsa_w4_gemm(x.data_ptr(), wc.data_ptr(), wz.data_ptr(), wsc.data_ptr(), y.data_ptr(),
+                    S > 1 ? part.data_ptr<float>() : nullptr, (int)M, (int)N, (int)K, (int)g, x.stride(0), y.stride(0), S,
+                    stream()),
+        "w4_gemm");
+  return y;
+}
+
+// the stored W4 weight as bf16((q - z) s) into out[:N, :K], a caller-provided scratch
+torch::Tensor w4_dequant(torch::Tensor wc, torch::Tensor wz, torch::Tensor wsc, int64_t N, int64_t K, int64_t g,
+                         torch::Tensor out) {
+  check_w4_stored(wc, wz, wsc, N, K, g, "w4_dequant");
+  TORCH_CHECK(N <= INT_MAX && K <= INT_MAX, "w4_dequant: shape");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kBFloat16 && out.dim() == 2 && out.stride(1) == 1 &&
+                  out.size(0) == N && out.size(1) == K && out.stride(0) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "w4_dequant: out is bf16 [N, K] with contiguous, 16-byte aligned rows");
+  check(dsa_w4_dequant(wc.data_ptr(), wz.data_ptr(), wsc.data_ptr(), out.data_ptr(), out.stride(0), (int)N, (int)K,
+                       (int)g, stream()),
+        "w4_dequant");
+  return out;
+}
+
 // out[M][N] (+)= a[K][M]^T b[K][N]  (csrc/gemm_nt.hip KM form: dW = dY^T X, token-major operands);
 // mode 2 = timing-only
 void gemm_km(torch::Tensor a, torch::Tensor b, torch::Tensor out, int64_t mode) {
@@ -1317,6 +1383,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "K slices mxfp4_gemm runs this shape with (0: unsupported)");
   m.def("mxfp4_dequant", &mxfp4_dequant, pybind11::arg("codes"), pybind11::arg("scales"), pybind11::arg("N"),
         pybind11::arg("K"), pybind11::arg("out"));
+  m.def("w4_gemm", &w4_gemm, pybind11::arg("x"), pybind11::arg("codes"), pybind11::arg("zeros"), pybind11::arg("scales"),
+        pybind11::arg("N"), pybind11::arg("K"), pybind11::arg("g"));
+  m.def("w4_gemm_supported", &w4_gemm_supported);
+  m.def("w4_gemm_form", [](int64_t M) { return dsa_w4_gemm_form((int)M); },
+        "16-row token blocks of the w4_gemm form that runs M rows (1, 4, 8 or 16)");
+  m.def("w4_gemm_split", [](int64_t M, int64_t N, int64_t K) { return dsa_w4_gemm_split((int)M, (int)N, (int)K); },
+        "K slices w4_gemm runs this shape with (0: unsupported)");
+  m.def("w4_dequant", &w4_dequant, pybind11::arg("codes"), pybind11::arg("zeros"), pybind11::arg("scales"),
+        pybind11::arg("N"), pybind11::arg("K"), pybind11::arg("g"), pybind11::arg("out"));
   m.def("swiglu_quant_fp8_rows", &swiglu_quant_fp8_rows, py::arg("gu"), py::arg("rs") = py::none(),
         py::arg("cs") = py::none());
   m.def("scale_rows_cols_", &scale_rows_cols_);

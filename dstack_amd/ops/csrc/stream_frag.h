@@ -1,5 +1,6 @@
 // What the weight-streaming decode GEMMs share (fp8_gemm.hip: fp8_stream_gemm with e4m3 weights,
-// mxfp4.hip: mxfp4_gemm with FP4 weights): fragment reads for v_mfma_scale_f32_16x16x128_f8f6f4
+// mxfp4.hip: mxfp4_gemm with FP4 weights; w4.hip: w4_gemm, bf16 MFMAs, takes the waits, the barrier, the
+// stores and the reduce): fragment reads for v_mfma_scale_f32_16x16x128_f8f6f4
 // from an LDS ring of 128-byte-row activation slots, a lane's accumulator holding 4 consecutive
 // output columns of one token row, fp32 split-K partials [S][M][N] and their reduce.  Each file
 // keeps its own swizzle, weight and scale loads and K-loop -- and its activation-offset loop, LDS-DMA
@@ -41,8 +42,15 @@ __device__ __forceinline__ i32x8 frag(const char* p0, const char* p1) {
   return i32x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 }
 
-// 4 consecutive output columns of one row, scaled by the row's xs (and the columns' ws) and rounded
-// to bf16: one 8-byte store
+// 4 consecutive output columns of one row, scaled by the row's xs (and the columns' ws) where there
+// are such scales, and rounded to bf16: one 8-byte store
+__device__ __forceinline__ void store_bf16x4(bf16_t* dst, const f32x4& v) {
+  unsigned short o[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) o[e] = f2bf(v[e]);
+  *reinterpret_cast<uint2*>(dst) =
+      uint2{(unsigned)o[0] | ((unsigned)o[1] << 16), (unsigned)o[2] | ((unsigned)o[3] << 16)};
+}
 __device__ __forceinline__ void store_bf16x4(bf16_t* dst, const f32x4& v, float xs) {
   unsigned short o[4];
 #pragma unroll
@@ -59,8 +67,9 @@ __device__ __forceinline__ void store_bf16x4(bf16_t* dst, const f32x4& v, float 
 }
 
 // y[m][n] = bf16(xs[m] (ws[n]) sum_s part[s][m][n]) in the order s = 0, 1, .. (no atomics: a seeded
-// request stays reproducible); 4 columns per thread.  WS: with per-column weight scales.
-template <bool WS>
+// request stays reproducible); 4 columns per thread.  WS: with per-column weight scales.  XS = false:
+// without the per-row scales either (w4.hip: bf16 activations), xs and ws unused.
+template <bool WS, bool XS = true>
 __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ part, const float* __restrict__ xs,
                                                      const float* __restrict__ ws, bf16_t* __restrict__ Y, int M,
                                                      int N, long ldy, int S) {
@@ -69,20 +78,21 @@ __global__ __launch_bounds__(256) void reduce_kernel(const float* __restrict__ p
     const int m = (int)(i / n4), n = (int)(i % n4) * 4;
     f32x4 a = *reinterpret_cast<const f32x4*>(part + (long)m * N + n);
     for (int s2 = 1; s2 < S; ++s2) a += *reinterpret_cast<const f32x4*>(part + ((long)s2 * M + m) * N + n);
-    const float xsc = xs[m];
-    if constexpr (WS)
-      store_bf16x4(Y + (long)m * ldy + n, a, xsc, *reinterpret_cast<const f32x4*>(ws + n));
+    if constexpr (!XS)
+      store_bf16x4(Y + (long)m * ldy + n, a);
+    else if constexpr (WS)
+      store_bf16x4(Y + (long)m * ldy + n, a, xs[m], *reinterpret_cast<const f32x4*>(ws + n));
     else
-      store_bf16x4(Y + (long)m * ldy + n, a, xsc);
+      store_bf16x4(Y + (long)m * ldy + n, a, xs[m]);
   }
 }
 
-template <bool WS>
+template <bool WS, bool XS = true>
 inline hipError_t reduce(const float* part, const float* xs, const float* ws, void* Y, int M, int N, long ldy, int S,
                          hipStream_t st) {
   const long work = (long)M * (N / 4);
   const int g = (int)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096);
-  reduce_kernel<WS><<<g, 256, 0, st>>>(part, xs, ws, (bf16_t*)Y, M, N, ldy, S);
+  reduce_kernel<WS, XS><<<g, 256, 0, st>>>(part, xs, ws, (bf16_t*)Y, M, N, ldy, S);
   return hipGetLastError();
 }
 

@@ -132,6 +132,86 @@ def mxfp4_linear(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor) -> 
     return y.to(torch.bfloat16).to(x.dtype)
 
 
+# ----------------------------------------------------------------------------------------------
+# W4A16 (AWQ checkpoints): unsigned 4-bit codes, one fp16 scale and one 4-bit zero point per group
+# of ``g`` elements along K and output row; activations stay bf16
+# ----------------------------------------------------------------------------------------------
+AWQ_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)  # nibble i of an AutoAWQ "GEMM" dword holds column 8 c + AWQ_ORDER[i]
+W4_GROUPS = (32, 64, 128)
+
+
+def _unpack_awq_dwords(packed: torch.Tensor) -> torch.Tensor:
+    """int32 [R, C] of 8 nibbles each -> uint8 [R, 8 C] in column order."""
+    shifts = torch.arange(0, 32, 4, dtype=torch.int32, device=packed.device)
+    nib = (packed.to(torch.int32)[..., None] >> shifts) & 15  # arithmetic shift: the mask drops the sign fill
+    inv = sorted(range(8), key=AWQ_ORDER.__getitem__)  # column j of a dword sits in nibble inv[j]
+    return nib[..., inv].to(torch.uint8).reshape(packed.shape[0], -1)
+
+
+def unpack_awq(qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor):
+    """An AutoAWQ "GEMM" 4-bit linear layer (in = K, out = N, group size g = K / rows of ``qzeros``):
+    ``qweight`` int32 [K, N/8], ``qzeros`` int32 [K/g, N/8], ``scales`` fp16 [K/g, N]; nibble i of
+    dword c of a row holds column ``8 c + (0, 2, 4, 6, 1, 3, 5, 7)[i]``.  Returns the canonical form of
+    W [N, K] = (q - z) * s: ``codes`` uint8 [N, K/2] (element 2j in the low nibble), ``zeros`` uint8
+    [N, K/g] (0..15) and ``scales`` fp16 [N, K/g]."""
+    K, N8 = qweight.shape
+    G = qzeros.shape[0]
+    if qweight.dtype != torch.int32 or qzeros.dtype != torch.int32 or tuple(qzeros.shape) != (G, N8) \
+            or tuple(scales.shape) != (G, 8 * N8) or G == 0 or K % G or K % 2:
+        raise ValueError(f"unpack_awq: qweight {tuple(qweight.shape)} {qweight.dtype}, qzeros {tuple(qzeros.shape)} "
+                         f"{qzeros.dtype}, scales {tuple(scales.shape)} are not one AWQ GEMM layer")
+    q = _unpack_awq_dwords(qweight).t()  # [N, K]
+    codes = (q[:, 0::2] | (q[:, 1::2] << 4)).contiguous()
+    zeros = _unpack_awq_dwords(qzeros).t().contiguous()
+    return codes, zeros, scales.to(torch.float16).t().contiguous()
+
+
+def _w4_nibbles(codes: torch.Tensor) -> torch.Tensor:
+    return torch.stack([codes & 15, codes >> 4], dim=-1).reshape(codes.shape[0], -1)
+
+
+def dequant_w4(codes: torch.Tensor, zeros: torch.Tensor, scales: torch.Tensor, g: int) -> torch.Tensor:
+    """fp32 [N, K] values ``(q - z) * s`` of a canonical W4 weight (``unpack_awq``, ``quant_w4``); exact:
+    an integer of at most 5 bits times an fp16 value."""
+    N, K = codes.shape[0], 2 * codes.shape[1]
+    if K % g or tuple(zeros.shape) != (N, K // g) or tuple(scales.shape) != (N, K // g):
+        raise ValueError(f"dequant_w4: zeros {tuple(zeros.shape)} / scales {tuple(scales.shape)} for [{N}, {K}], g = {g}")
+    q = _w4_nibbles(codes).reshape(N, K // g, g).float()
+    return ((q - zeros.float()[..., None]) * scales.float()[..., None]).reshape(N, K)
+
+
+def w4_linear(x: torch.Tensor, codes: torch.Tensor, zeros: torch.Tensor, scales: torch.Tensor, g: int) -> torch.Tensor:
+    """x @ W^T for a canonical W4 weight: x times the fp32 dequantized weight, the products accumulated
+    in fp64 and rounded once to x's dtype -- the CPU path of the serving engine, whose unquantized
+    GEMMs are accumulated the same way, so that a row's result does not depend on how many rows are
+    multiplied with it."""
+    return (x.double() @ dequant_w4(codes, zeros, scales, g).double().t()).to(x.dtype)
+
+
+def quant_w4(w: torch.Tensor, g: int = 128):
+    """Canonical W4 form (``codes``, ``zeros``, ``scales``: see ``unpack_awq``) of ``w`` [N, K] by plain
+    asymmetric min/max round-to-nearest per group of ``g`` along K: s = fp16((max - min) / 15),
+    z = clamp(round(-min / s), 0, 15), q = clamp(round(w / s) + z, 0, 15); a group whose range is zero
+    (or underflows fp16) gets s = 1, z = 0, q = clamp(round(w), 0, 15).
+
+    This is NOT AWQ: there is no calibration data, no activation-aware channel scaling and no
+    clipping search.  It exists to give the built-in random-weight models and the tests a 4-bit
+    weight to run on; a served model should come as a calibrated AWQ checkpoint."""
+    N, K = w.shape
+    if g not in W4_GROUPS or K % g or K % 2:
+        raise ValueError(f"quant_w4: K = {K} is not a multiple of the group size {g} (one of {W4_GROUPS})")
+    x = w.float().reshape(N, K // g, g)
+    mn, mx = x.amin(dim=-1), x.amax(dim=-1)
+    s = ((mx - mn) / 15).to(torch.float16)
+    flat = s == 0
+    s = torch.where(flat, torch.ones_like(s), s)
+    sf = s.float()
+    z = torch.where(flat, torch.zeros_like(sf), torch.round(-mn / sf).clamp(0, 15))
+    q = (torch.round(x / sf[..., None]) + z[..., None]).clamp(0, 15).to(torch.uint8).reshape(N, K // 2, 2)
+    codes = q[..., 0] | (q[..., 1] << 4)
+    return codes.contiguous(), z.to(torch.uint8).contiguous(), s.contiguous()
+
+
 def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     return F.cross_entropy(logits.float(), target, reduction="mean")
 

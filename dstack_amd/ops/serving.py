@@ -813,3 +813,63 @@ def mxfp4_unshuffle(codes: torch.Tensor, scales: torch.Tensor, K: int | None = N
     if K is not None and K != Kp:
         c, s = c[:, : K // 2].contiguous(), s[:, : K // 32].contiguous()
     return c, s
+
+
+W4_NIBBLE_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)  # nibble p of a stored dword holds K element W4_NIBBLE_ORDER[p] of its 8
+
+
+def w4_shuffle(codes: torch.Tensor, zeros: torch.Tensor, scales: torch.Tensor, g: int):
+    """The stored form of a canonical W4 weight (``ops.reference.unpack_awq`` / ``quant_w4``: ``codes``
+    uint8 [N, K/2], ``zeros`` uint8 [N, K/g], ``scales`` fp16 [N, K/g]) -- the order ``w4_gemm``
+    (``csrc/w4.hip``) streams it in.  A K-step is 128 elements: four 32-wide MFMA steps ``kk``.  Lane
+    ``r + 16 gq`` of a wave holds weight row r of a 16-row block and, of MFMA step kk, the K elements
+    ``[128 t + 32 kk + 8 gq, + 8)``; its accumulator holds rows ``4 gq + e`` (e = 0..3) of the block:
+
+    * codes: per 16-row block and K-step the 1 KiB of the 64 lanes' 16 bytes in lane order, the steps
+      of a block consecutive over K.  A lane's dword kk holds its 8 elements of MFMA step kk, element
+      ``(0, 2, 4, 6, 1, 3, 5, 7)[p]`` in nibble p (bits 4p .. 4p+3): ``(dword >> 4 i) & 0x000F000F`` is
+      then elements 2i (low half) and 2i + 1 (high half), one MFMA operand register;
+    * scales (fp16) and zeros (one byte each, holding ``128 + z``: the kernel multiplies bf16 values
+      ``128 + q`` and subtracts that): per 16-row block and K-step, for lane group gq = 0..3, for each
+      of the step's 128 / g groups G, the values of rows ``4 gq + e``, e = 0..3 -- the ``8 * 128 / g``
+      and ``4 * 128 / g`` bytes a lane loads at once, at ``((b * steps + t) * 4 + gq)`` times that size.
+
+    N % 16 == 0, K % g == 0, g in (32, 64, 128).  K is padded to a multiple of 128 (Kp) with zero
+    codes, zeros and scales; returns contiguous (codes [N, Kp/2], zeros [N, Kp/g], scales [N, Kp/g])
+    (done once, when the weights are loaded; the engine keeps only this form).  Stored bytes:
+    ``N Kp / 2 + N Kp / g * (2 + 1)`` -- a zero point takes a byte, not a nibble."""
+    N, K2 = codes.shape
+    K = 2 * K2
+    assert g in (32, 64, 128) and N % 16 == 0 and K % g == 0, (N, K, g)
+    assert tuple(zeros.shape) == (N, K // g) and tuple(scales.shape) == (N, K // g), (zeros.shape, scales.shape)
+    assert codes.dtype == torch.uint8 and zeros.dtype == torch.uint8 and scales.dtype == torch.float16
+    pad = -K % 128
+    if pad:
+        codes = torch.nn.functional.pad(codes, (0, pad // 2))
+        zeros = torch.nn.functional.pad(zeros, (0, pad // g))
+        scales = torch.nn.functional.pad(scales, (0, pad // g))
+        K, K2 = K + pad, K2 + pad // 2
+    T, GS = K // 128, 128 // g
+    q = torch.stack([codes & 15, codes >> 4], dim=-1).reshape(N // 16, 16, T, 4, 4, 8)  # (blk, r, t, kk, gq, j)
+    q = q.permute(0, 2, 4, 1, 3, 5)[..., list(W4_NIBBLE_ORDER)]  # (blk, t, gq, r, kk, p)
+    c = (q[..., 0::2] | (q[..., 1::2] << 4)).contiguous().view(N, K2)
+    z = (zeros + 128).reshape(N // 16, 4, 4, T, GS).permute(0, 3, 1, 4, 2).contiguous().view(N, K // g)  # (blk, t, gq, G, e)
+    s = scales.reshape(N // 16, 4, 4, T, GS).permute(0, 3, 1, 4, 2).contiguous().view(N, K // g)
+    return c, z, s
+
+
+def w4_unshuffle(codes: torch.Tensor, zeros: torch.Tensor, scales: torch.Tensor, g: int, K: int | None = None):
+    """Inverse of :func:`w4_shuffle`: the canonical (codes, zeros, scales) of a stored weight; ``K``: the
+    weight's K where the stored form is padded."""
+    N, K2 = codes.shape
+    Kp = 2 * K2
+    T, GS = Kp // 128, 128 // g
+    p = torch.stack([codes & 15, codes >> 4], dim=-1).reshape(N // 16, T, 4, 16, 4, 8)  # (blk, t, gq, r, kk, p)
+    inv = sorted(range(8), key=W4_NIBBLE_ORDER.__getitem__)
+    q = p[..., inv].permute(0, 3, 1, 4, 2, 5).reshape(N, K2, 2)  # (blk, r, t, kk, gq, j)
+    c = (q[..., 0] | (q[..., 1] << 4)).contiguous()
+    z = (zeros - 128).reshape(N // 16, T, 4, GS, 4).permute(0, 2, 4, 1, 3).contiguous().view(N, Kp // g)
+    s = scales.reshape(N // 16, T, 4, GS, 4).permute(0, 2, 4, 1, 3).contiguous().view(N, Kp // g)
+    if K is not None and K != Kp:
+        c, z, s = c[:, : K // 2].contiguous(), z[:, : K // g].contiguous(), s[:, : K // g].contiguous()
+    return c, z, s

@@ -23,10 +23,12 @@ def main(argv=None):
     ap.add_argument("--gpu-memory-utilization", type=float, default=0.90)
     ap.add_argument("--no-graphs", action="store_true", help="run decode steps eagerly (no hipGraph capture)")
     ap.add_argument("--seed", type=int, default=0, help="random-init seed for built-in configs")
-    ap.add_argument("--quantization", choices=["fp8", "mxfp4"], default=None,
+    ap.add_argument("--quantization", choices=["fp8", "mxfp4", "awq"], default=None,
                     help="fp8: e4m3 projection weights with per-channel scales, per-token activation scales; "
                          "mxfp4: OCP MXFP4 projection weights (e2m1, one E8M0 scale per 32), e4m3 activations "
-                         "on the block-scaled FP4 decode GEMM")
+                         "on the block-scaled FP4 decode GEMM; awq: an AutoAWQ 4-bit checkpoint (qweight / qzeros / "
+                         "scales, GEMM packing) on the W4A16 decode GEMM with bf16 activations -- selected by "
+                         "itself when the checkpoint's config.json says so")
     ap.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto",
                     help="fp8: e4m3 paged KV cache (half the bytes per decode step, twice the tokens)")
     ap.add_argument("--enable-prefix-caching", action="store_true",
@@ -34,7 +36,7 @@ def main(argv=None):
                          "not with tensor parallel")
     ap.add_argument("--lora-modules", nargs="+", default=[], metavar="NAME=PATH",
                     help="LoRA adapters (PEFT directories) to serve next to the base model; a request picks one "
-                         "by its `model`; not with --quantization fp8 / mxfp4 or tensor parallel")
+                         "by its `model`; not with --quantization fp8 / mxfp4 / awq or tensor parallel")
     ap.add_argument("--max-lora-rank", type=int, default=64,
                     help="largest adapter rank accepted (the adapter stacks are padded to 8, 16, 32 or 64)")
     ap.add_argument("--speculative-ngram", type=int, default=0, metavar="K",

@@ -33,7 +33,7 @@ import torch
 import torch.distributed as dist
 
 from dstack_amd.ops import serving as sops
-from dstack_amd.serving.model import ServingLlama, load_spec
+from dstack_amd.serving.model import ServingLlama, check_awq, load_spec
 
 
 @dataclass
@@ -210,17 +210,26 @@ class LLMEngine:
         if quantization == "mxfp4" and tp_group is not None:
             raise ValueError("quantization=\"mxfp4\" is not supported with tensor parallel yet")
         spec = load_spec(model)
+        if spec.awq is not None or quantization == "awq":  # an AWQ checkpoint selects the mode by itself
+            check_awq(spec, quantization)
+            quantization = "awq"
+            if kw.get("lora_modules"):
+                _check_lora(quantization, tp_group)
+            if tp_group is not None:
+                raise ValueError("quantization=\"awq\" is not supported with tensor parallel yet")
         device = device or ("cuda" if torch.cuda.is_available() else "cpu")
         m = ServingLlama(spec, device, max_model_len=max_model_len, tp_group=tp_group, quantization=quantization,
                          kv_cache_dtype=kv_cache_dtype)
         if spec.path:
-            m.load_hf()
+            m.load_hf()  # (an AWQ checkpoint arrives 4-bit: nothing to quantize below)
         else:
             m.init_random(seed)
         if quantization == "fp8":
             m.quantize_fp8()  # before the KV cache is sized: the freed bf16 bytes become KV pages
         elif quantization == "mxfp4":
             m.quantize_mxfp4()
+        elif quantization == "awq" and not spec.path:
+            m.quantize_awq()  # built-in random weights: min/max rounding, so the benchmarks run without a checkpoint
         return cls(m, eos_token_ids=spec.eos_token_ids, **kw)
 
     # ------------------------------------------------------------------------------------------
@@ -1049,6 +1058,8 @@ def _check_lora(quantization, tp_group):
         raise ValueError("LoRA adapters are not supported with quantization=\"mxfp4\": the decode GEMM takes e4m3 "
                          "activations against FP4 weights, and the adapter kernels are written for bf16 "
                          "projections (an fp8 KV cache is fine)")
+    if quantization == "awq":
+        raise ValueError("LoRA adapters are not supported with quantization=\"awq\" yet (an fp8 KV cache is fine)")
     if tp_group is not None:
         raise ValueError("LoRA adapters are not supported with tensor parallel yet")
 

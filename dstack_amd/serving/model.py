@@ -81,6 +81,64 @@ class Mxfp4Weight:
         return sops.mxfp4_unshuffle(self.codes, self.scales, self.K)
 
 
+class Awq4Weight:
+    """A W4A16 linear weight [N, K] of an AWQ checkpoint: W = (q - z) * s with unsigned 4-bit codes q
+    and, per group of ``g`` elements along K and output row, an fp16 scale s and a zero point z.  Kept
+    only in the order the decode GEMM streams it (``ops.serving.w4_shuffle``): ``codes`` uint8
+    [N, Kp/2], ``zeros`` uint8 [N, Kp/g] (a byte each, holding 128 + z) and ``scales`` fp16 [N, Kp/g],
+    Kp = K rounded up to 128 (zero codes)."""
+
+    __slots__ = ("codes", "zeros", "scales", "N", "K", "g")
+
+    def __init__(self, codes: torch.Tensor, zeros: torch.Tensor, scales: torch.Tensor, N: int, K: int, g: int):
+        self.codes, self.zeros, self.scales, self.N, self.K, self.g = codes, zeros, scales, int(N), int(K), int(g)
+
+    @property
+    def shape(self):
+        return torch.Size((self.N, self.K))
+
+    def nbytes(self) -> int:
+        """N Kp / 2 + N Kp / g * (2 + 1): a stored zero point takes a byte, not a nibble."""
+        return self.codes.numel() + self.zeros.numel() + 2 * self.scales.numel()
+
+    def canonical(self):
+        """(codes [N, K/2], zeros [N, K/g], scales [N, K/g]) in the canonical order (``ops.reference.unpack_awq``)."""
+        return sops.w4_unshuffle(self.codes, self.zeros, self.scales, self.g, self.K)
+
+
+@dataclass
+class AwqConfig:
+    """``quantization_config`` of an AutoAWQ checkpoint, as far as it is supported: 4 bits, "GEMM"
+    packing, zero points, one group size for every projection."""
+
+    group_size: int = 128
+
+
+def _awq_config(qc: dict) -> AwqConfig:
+    """Check an HF ``quantization_config``; every unsupported value is an error that names its field."""
+    method = str(qc.get("quant_method", "")).lower()
+    if method != "awq":
+        raise ValueError(f"unsupported quantization_config: quant_method = {qc.get('quant_method')!r} (only \"awq\" "
+                         "checkpoints are loaded; GPTQ, compressed-tensors and others are not)")
+    bits = qc.get("bits", qc.get("w_bit"))
+    if bits != 4:
+        raise ValueError(f"unsupported AWQ quantization_config: bits = {bits!r} (only 4)")
+    version = str(qc.get("version", "gemm")).lower()
+    if version != "gemm":
+        raise ValueError(f"unsupported AWQ quantization_config: version = {qc.get('version')!r} (only the \"GEMM\" "
+                         "packing; GEMV and Marlin repacks are not)")
+    if not qc.get("zero_point", True):
+        raise ValueError("unsupported AWQ quantization_config: zero_point = false (only asymmetric checkpoints "
+                         "with qzeros)")
+    g = qc.get("group_size", qc.get("q_group_size", 128))
+    if g not in ref.W4_GROUPS:
+        raise ValueError(f"unsupported AWQ quantization_config: group_size = {g!r} (one of {ref.W4_GROUPS})")
+    if qc.get("modules_to_not_convert"):
+        raise ValueError(f"unsupported AWQ quantization_config: modules_to_not_convert = "
+                         f"{qc['modules_to_not_convert']!r} (every projection must be quantized)")
+    return AwqConfig(group_size=int(g))
+
+
 class Fp8Act:
     """Activations already in e4m3 with per-row scales (``q`` uint8 [M, K], ``s`` fp32 [M]),
     produced by the fused add+RMSNorm->fp8 kernel for the next fp8 GEMM."""
@@ -147,13 +205,15 @@ class ModelSpec:
     path: str | None = None  # HF checkpoint directory (None: random init)
     family: str = "llama"  # llama | mistral | qwen2 (same block; qwen2 adds q/k/v biases)
     qkv_bias: bool = False
+    awq: AwqConfig | None = None  # the checkpoint's projections are AWQ 4-bit (config.json quantization_config)
 
 
 def load_spec(model: str) -> ModelSpec:
     """``model`` is a built-in config name (``llama-3-8b``, ``llama-3-70b``, …: random weights) or an
     HF checkpoint directory (``config.json`` + ``*.safetensors``) of the Llama block family: Llama
     2/3/3.x, Mistral (sliding-window models are served up to their window) and Qwen2 / Qwen2.5
-    (q/k/v projection biases)."""
+    (q/k/v projection biases).  A checkpoint whose ``config.json`` has a ``quantization_config`` must be
+    an AutoAWQ 4-bit "GEMM" one (``ModelSpec.awq``); anything else in it is an error naming the field."""
     if model in CONFIGS:
         return ModelSpec(CONFIGS[model], eos_token_ids=())
     cfg_path = os.path.join(model, "config.json")
@@ -200,11 +260,23 @@ def load_spec(model: str) -> ModelSpec:
         raise ValueError(f"unsupported rope_scaling {rs}")
     eos = hf.get("eos_token_id")
     eos_ids = tuple(eos) if isinstance(eos, list) else ((eos,) if eos is not None else ())
+    awq = _awq_config(hf["quantization_config"]) if hf.get("quantization_config") else None
     return ModelSpec(cfg, scaling, bool(hf.get("tie_word_embeddings", False)), hf.get("bos_token_id"), eos_ids,
-                     path=model, family=family, qkv_bias=family == "qwen2")
+                     path=model, family=family, qkv_bias=family == "qwen2", awq=awq)
 
 
 SUPPORTED_FAMILIES = ("llama", "mistral", "qwen2")
+
+
+def check_awq(spec: ModelSpec, quantization: str | None):
+    """``quantization`` against what the checkpoint holds: an AWQ checkpoint is served as it is, and
+    there is no AWQ calibrator here to turn an unquantized checkpoint into one."""
+    if spec.awq is not None and quantization not in (None, "awq"):
+        raise ValueError(f"quantization={quantization!r} on an AWQ checkpoint ({spec.path}: config.json "
+                         "quantization_config): its projections are 4-bit already; use quantization=\"awq\" or none")
+    if quantization == "awq" and spec.path and spec.awq is None:
+        raise ValueError(f"quantization=\"awq\" needs an AWQ checkpoint, and {spec.path} has no quantization_config in "
+                         "its config.json: there is no AWQ calibration here (quantize it with AutoAWQ first)")
 
 
 class ServingLlama:
@@ -213,10 +285,13 @@ class ServingLlama:
 
     def __init__(self, spec: ModelSpec, device, dtype=None, max_model_len: int | None = None, tp_group=None,
                  quantization: str | None = None, kv_cache_dtype: str = "auto"):
-        if quantization not in (None, "fp8", "mxfp4"):
-            raise ValueError(f"unsupported quantization {quantization!r} (supported: fp8, mxfp4)")
-        if quantization == "mxfp4" and tp_group is not None:
-            raise ValueError("quantization=\"mxfp4\" is not supported with tensor parallel yet")
+        if quantization is None and spec.awq is not None:
+            quantization = "awq"  # the checkpoint says so itself
+        if quantization not in (None, "fp8", "mxfp4", "awq"):
+            raise ValueError(f"unsupported quantization {quantization!r} (supported: fp8, mxfp4, awq)")
+        check_awq(spec, quantization)
+        if quantization in ("mxfp4", "awq") and tp_group is not None:
+            raise ValueError(f"quantization=\"{quantization}\" is not supported with tensor parallel yet")
         if kv_cache_dtype not in ("auto", "fp8"):
             raise ValueError(f"unsupported kv_cache_dtype {kv_cache_dtype!r} (supported: auto, fp8)")
         self.quantization = quantization
@@ -290,11 +365,14 @@ class ServingLlama:
             self.lm_head = self.embed[self.tp_rank * self.V : (self.tp_rank + 1) * self.V]
         else:
             self.lm_head = self._empty(self.V, d)
-        self.layers = [
-            dict(attn_norm=self._empty(d), wqkv=self._empty(self.NH * hd, d), wo=self._empty(d, self.H * hd),
-                 ffn_norm=self._empty(d), wgu=self._empty(2 * self.F, d), wdown=self._empty(d, self.F))
-            for _ in range(cfg.n_layers)
-        ]
+        if self.spec.awq is not None:  # the projections arrive 4-bit (load_hf): no bf16 copy is ever made
+            self.layers = [dict(attn_norm=self._empty(d), ffn_norm=self._empty(d)) for _ in range(cfg.n_layers)]
+        else:
+            self.layers = [
+                dict(attn_norm=self._empty(d), wqkv=self._empty(self.NH * hd, d), wo=self._empty(d, self.H * hd),
+                     ffn_norm=self._empty(d), wgu=self._empty(2 * self.F, d), wdown=self._empty(d, self.F))
+                for _ in range(cfg.n_layers)
+            ]
         if self.spec.qkv_bias:
             for L in self.layers:
                 L["bqkv"] = self._empty(self.NH * hd)
@@ -361,6 +439,10 @@ class ServingLlama:
             raise FileNotFoundError(f"no *.safetensors in {path}")
         H, KVH, hd, f = self.H, self.KVH, self.D, self.F  # local (per tensor-parallel rank)
         seen = set()
+        awq = self.spec.awq
+        # AWQ checkpoint: a layer's 7 x (qweight, qzeros, scales) are collected on the host and turned
+        # into its four stored weights as soon as the last one has arrived (``_put_awq_layer``)
+        awq_pending: dict[int, dict] = {}
 
         def put(dst, src, kind=None):
             if kind is not None:
@@ -383,7 +465,20 @@ class ServingLlama:
                         parts = name.split(".")
                         L = self.layers[int(parts[2])]
                         key = ".".join(parts[3:])
-                        if key == "input_layernorm.weight":
+                        proj, _, kind = key.rpartition(".")
+                        if proj in self.AWQ_PROJ and (kind in self.AWQ_KINDS or (kind == "weight" and awq)):
+                            if awq is None:
+                                raise ValueError(f"unexpected tensor {name}: an AWQ tensor in a checkpoint whose "
+                                                 "config.json has no quantization_config")
+                            if kind == "weight":
+                                raise ValueError(f"unexpected tensor {name}: config.json says the checkpoint is AWQ, so "
+                                                 f"this projection must come as {', '.join(self.AWQ_KINDS)}")
+                            li = int(parts[2])
+                            got = awq_pending.setdefault(li, {})
+                            got[(proj, kind)] = self._check_awq_tensor(name, proj, kind, t)
+                            if len(got) == len(self.AWQ_PROJ) * len(self.AWQ_KINDS):
+                                self._put_awq_layer(L, awq_pending.pop(li))
+                        elif key == "input_layernorm.weight":
                             put(L["attn_norm"], t)
                         elif key == "post_attention_layernorm.weight":
                             put(L["ffn_norm"], t)
@@ -414,14 +509,86 @@ class ServingLlama:
         if not self.spec.tie_embeddings:
             expected.add("lm_head.weight")
         for i in range(self.cfg.n_layers):
-            expected |= {f"model.layers.{i}.{k}.weight" for k in (
-                "input_layernorm", "post_attention_layernorm", "self_attn.q_proj", "self_attn.k_proj",
-                "self_attn.v_proj", "self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj")}
+            expected |= {f"model.layers.{i}.{k}.weight" for k in ("input_layernorm", "post_attention_layernorm")}
+            expected |= {f"model.layers.{i}.{k}.{kind}" for k in self.AWQ_PROJ
+                         for kind in (self.AWQ_KINDS if awq else ("weight",))}
             if self.spec.qkv_bias:
                 expected |= {f"model.layers.{i}.self_attn.{p}_proj.bias" for p in "qkv"}
         missing = expected - seen
         if missing:
             raise ValueError(f"checkpoint {path} is missing {len(missing)} tensors, e.g. {sorted(missing)[:3]}")
+        if awq:
+            self._alloc_w4_scratch()
+        return self
+
+    # the projections of an AWQ checkpoint (HF module name -> which rows / columns of the fused weights)
+    AWQ_PROJ = {"self_attn.q_proj": "q", "self_attn.k_proj": "k", "self_attn.v_proj": "v", "self_attn.o_proj": "wo",
+                "mlp.gate_proj": "gate", "mlp.up_proj": "up", "mlp.down_proj": "wdown"}
+    AWQ_KINDS = ("qweight", "qzeros", "scales")
+
+    def _check_awq_tensor(self, name: str, proj: str, kind: str, t: torch.Tensor) -> torch.Tensor:
+        """Shape and dtype of one AWQ tensor against the spec (AutoAWQ "GEMM": qweight int32 [K, N/8],
+        qzeros int32 [K/g, N/8], scales fp16 [K/g, N])."""
+        d, hd, g = self.cfg.dim, self.D, self.spec.awq.group_size
+        N, K = {"q": (self.H * hd, d), "k": (self.KVH * hd, d), "v": (self.KVH * hd, d), "wo": (d, self.H * hd),
+                "gate": (self.F, d), "up": (self.F, d), "wdown": (d, self.F)}[self.AWQ_PROJ[proj]]
+        if K % g or N % 8:
+            raise ValueError(f"{name}: a [{N}, {K}] projection has no whole groups of {g} / dwords of 8 columns")
+        shape, dtype = {"qweight": ((K, N // 8), torch.int32), "qzeros": ((K // g, N // 8), torch.int32),
+                        "scales": ((K // g, N), torch.float16)}[kind]
+        if tuple(t.shape) != shape or t.dtype != dtype:
+            raise ValueError(f"{name}: expected {dtype} {list(shape)} for a [{N}, {K}] projection with group_size {g}, "
+                             f"got {t.dtype} {list(t.shape)}")
+        return t
+
+    def _awq_weight(self, codes, zeros, scales, g: int) -> Awq4Weight:
+        """The stored, uploaded form of a canonical W4 weight."""
+        N, K = codes.shape[0], 2 * codes.shape[1]
+        if N % 16:
+            raise ValueError(f"quantization=\"awq\": a projection of {N} output rows is no multiple of 16")
+        return Awq4Weight(*(t.to(self.device) for t in sops.w4_shuffle(codes, zeros, scales, g)), N, K, g)
+
+    def _put_awq_layer(self, L: dict, got: dict):
+        """One layer's AWQ tensors -> its four stored weights: each projection is unpacked on the host
+        to the canonical form, q/k/v and gate/up are concatenated along N there, and the result is
+        shuffled and uploaded; the temporaries die with this call.  No bf16 copy is made."""
+        g = self.spec.awq.group_size
+
+        def fused(*projs):
+            parts = [ref.unpack_awq(*(got[(p, kind)] for kind in self.AWQ_KINDS)) for p in projs]
+            return self._awq_weight(*(torch.cat([p[i] for p in parts]) for i in range(3)), g)
+
+        L["wqkv"] = fused("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj")
+        L["wo"] = fused("self_attn.o_proj")
+        L["wgu"] = fused("mlp.gate_proj", "mlp.up_proj")
+        L["wdown"] = fused("mlp.down_proj")
+
+    def _alloc_w4_scratch(self):
+        """The bf16 scratch the prefill-sized W4 GEMMs dequantize into (the largest projection; a
+        workspace, not counted as weight bytes)."""
+        big = max(L[k].N * L[k].K for L in self.layers for k in self.FP8_KEYS)
+        self._w4_scratch = torch.empty(big, dtype=torch.bfloat16, device=self.device) if self.hip else None
+
+    @torch.no_grad()
+    def quantize_awq(self, g: int = 128):
+        """Built-in (random-weight) architectures only: every layer's projections (``FP8_KEYS``) to W4
+        by ``ref.quant_w4`` -- plain min/max rounding per group, NOT AWQ calibration; it gives the
+        benchmarks a 4-bit model to run without a checkpoint -- layer by layer, freeing each bf16
+        tensor as it goes.  One copy is kept, in the decode GEMM's order."""
+        for L in self.layers:
+            for k in self.FP8_KEYS:
+                w = L[k]
+                if isinstance(w, Awq4Weight):
+                    continue
+                N, K = w.shape
+                if K % g:
+                    raise ValueError(f"quantization=\"awq\": projection {k} [{N}, {K}] needs K % {g} == 0 (one scale "
+                                     "and zero point per group)")
+                L[k] = self._awq_weight(*ref.quant_w4(w, g), g)
+                del w
+            if self.device.type == "cuda":
+                torch.cuda.empty_cache()
+        self._alloc_w4_scratch()
         return self
 
     # projections that fp8 quantization converts (the LM head, embedding and norms stay bf16)
@@ -523,7 +690,7 @@ class ServingLlama:
         n = sum(t.numel() * t.element_size() for t in ts)
         for L in self.layers:
             for t in L.values():
-                n += t.nbytes() if isinstance(t, (Fp8Weight, Mxfp4Weight)) else t.numel() * t.element_size()
+                n += t.nbytes() if isinstance(t, (Fp8Weight, Mxfp4Weight, Awq4Weight)) else t.numel() * t.element_size()
         for L in self.lora:
             n += sum(t.numel() * t.element_size() for ab in L.values() for t in ab)
         return n
@@ -546,6 +713,9 @@ class ServingLlama:
         if self.quantization == "mxfp4":
             raise ValueError("LoRA adapters are not supported with quantization=\"mxfp4\": the adapter kernels are "
                              "written for bf16 projections")
+        if self.quantization == "awq":
+            raise ValueError("LoRA adapters are not supported with quantization=\"awq\" yet (inputs and outputs of "
+                             "the W4A16 projections are bf16, so nothing stands in the way but the work)")
         if self.tp > 1:
             raise ValueError("LoRA adapters are not supported with tensor parallel yet")
         if max_loras < 1:
@@ -712,6 +882,8 @@ class ServingLlama:
         prefill use hipBLASLt."""
         if isinstance(w, Mxfp4Weight):
             return self._mm_mxfp4(x, w)
+        if isinstance(w, Awq4Weight):
+            return self._mm_w4(x, w)
         if isinstance(w, Fp8Weight) or isinstance(x, Fp8Act):
             return self._mm_fp8(x, w)
         if self.hip and self.gemv and x.shape[0] == 1:
@@ -742,6 +914,25 @@ class ServingLlama:
             xq, xs = C.quant_fp8_rows(x)
             return C.mxfp4_gemm(xq.view(torch.uint8), xs, w.codes, w.scales, w.N, w.K)
         wd = C.mxfp4_dequant(w.codes, w.scales, w.N, w.K, self._mx_scratch[: w.N * w.K].view(w.N, w.K))
+        return x @ wd.t()
+
+    def _mm_w4(self, x, w: Awq4Weight):
+        """``x @ W^T`` for a W4A16 weight.  Up to 256 rows (a decode batch or a verify step) of a shape
+        the kernel covers: the bf16 activations as they are (nothing is quantized per token) times the
+        stored weight on ``w4_gemm`` (``csrc/w4.hip``), the scales in fp32.  Otherwise (prefill-sized
+        batches, other shapes): the weight is dequantized into the bf16 scratch and multiplied by the
+        bf16 GEMM -- there ``(q - z) * s`` is rounded to bf16 before it is multiplied, one rounding more
+        than the decode kernel makes, so the two paths differ as the prefill and decode GEMMs of the
+        other modes do.  CPU: ``ref.w4_linear`` for every row count."""
+        if not self.hip:
+            return ref.w4_linear(x, *w.canonical(), w.g)
+        C = _ext.require()
+        M = x.shape[0]
+        if M <= 256 and x.dtype == torch.bfloat16 and C.w4_gemm_supported(M, w.N, w.K, w.g):
+            if x.stride(-1) != 1 or x.stride(0) % 8 or x.data_ptr() % 16:
+                x = x.contiguous()
+            return C.w4_gemm(x, w.codes, w.zeros, w.scales, w.N, w.K, w.g)
+        wd = C.w4_dequant(w.codes, w.zeros, w.scales, w.N, w.K, w.g, self._w4_scratch[: w.N * w.K].view(w.N, w.K))
         return x @ wd.t()
 
     def _mm_fp8(self, x, w: Fp8Weight, defer: str | None = None):
@@ -921,7 +1112,7 @@ class ServingLlama:
                 # prefill-sized: the GEMM's row-wise scales are applied by the RoPE / cache-write kernel
                 r = self._mm_fp8(h, wq, defer="raw")
             else:
-                r = self._mm(h, wq) if isinstance(wq, (Fp8Weight, Mxfp4Weight)) else h @ wq.t()
+                r = self._mm(h, wq) if isinstance(wq, (Fp8Weight, Mxfp4Weight, Awq4Weight)) else h @ wq.t()
                 if lora is not None:  # before the bias and the RoPE / cache write
                     self._lora_add(li, "wqkv", h, r, lora)
             if isinstance(r, RawScaled):
