@@ -29,6 +29,9 @@ ROOT = HERE.parent.parent
 BUILD = ROOT / "build" / "ops"
 ARCH = os.environ.get("DSTACK_AMD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+# units compiled without the packed fp32 instructions (v_pk_{add,mul,fma}_f32): beside MFMAs they cost
+# issue cycles (csrc/w4.hip keeps its folds apart by hand); the older units keep the flags they were tuned with
+NO_PACKED_FP32 = {"moe"}
 
 
 def _torch_paths():
@@ -90,6 +93,8 @@ def _plan(keep_asm: bool = False):
     for src in kernels:
         obj = BUILD / (src.stem + ".o")
         cmd = [HIPCC, *common, "-c", str(src), "-o", str(obj)]
+        if src.stem in NO_PACKED_FP32:
+            cmd += ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
         if keep_asm:
             cmd += ["-save-temps=obj", "-Rpass-analysis=kernel-resource-usage"]
         units.append((obj, cmd, _digest([src, *headers], cmd)))

@@ -118,6 +118,16 @@ int dsa_w4_gemm_split(int, int, int);
 hipError_t dsa_w4_gemm(const void*, const void*, const void*, const void*, void*, float*, int, int, int, int, long, long,
                        int, hipStream_t);
 hipError_t dsa_w4_dequant(const void*, const void*, const void*, void*, long, int, int, int, hipStream_t);
+int dsa_moe_gemm_form(int);
+bool dsa_moe_gemm_supported(int, int, int);
+int dsa_moe_gemm_split(int, int, int, int, int);
+hipError_t dsa_moe_gemm(const void*, long, int, int, const void*, const int*, const int*, float*, int, int, int, int, int,
+                        int, hipStream_t);
+hipError_t dsa_moe_lists(const int*, const int*, int*, int*, int, int, int, hipStream_t);
+hipError_t dsa_moe_route(const void*, long, const void*, const int*, int*, float*, int*, int*, int, int, int, int,
+                         hipStream_t);
+hipError_t dsa_moe_swiglu(const float*, const int*, void*, int, int, int, int, hipStream_t);
+hipError_t dsa_moe_combine(const float*, const float*, const int*, void*, long, int, int, int, int, hipStream_t);
 }
 
 namespace {
@@ -805,6 +815,116 @@ torch::Tensor w4_dequant(torch::Tensor wc, torch::Tensor wz, torch::Tensor wsc, 
   return out;
 }
 
+// ---- sparse mixture-of-experts MLP of the decode step (csrc/moe.hip); every output is the caller's ----
+void check_moe(const torch::Tensor& t, torch::ScalarType ty, std::initializer_list<int64_t> shape, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == ty && t.is_contiguous() && t.sizes() == torch::IntArrayRef(shape) &&
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              what, ": a contiguous, 16-byte aligned ROCm tensor of the documented dtype and shape");
+}
+
+void check_moe_rows(const torch::Tensor& x, int64_t cols, const char* what) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 && x.dim() == 2 && x.size(1) == cols &&
+                  x.stride(1) == 1 && x.stride(0) % 8 == 0 && x.stride(0) >= cols &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              what, ": bf16 rows, contiguous and 16-byte aligned");
+}
+
+void check_moe_dims(int64_t R, int64_t k, int64_t E, const char* what) {
+  TORCH_CHECK(R >= 1 && R <= 256 && k >= 1 && k <= 8 && E >= k && E <= 64, what,
+              ": 1 <= rows <= 256, 1 <= experts per token <= 8, experts per token <= experts <= 64");
+}
+
+bool moe_gemm_supported(int64_t R, int64_t N, int64_t K) {
+  return R <= INT_MAX && N <= INT_MAX && K <= INT_MAX && dsa_moe_gemm_supported((int)R, (int)N, (int)K);
+}
+
+// counts [E], lists [E, R] from topk_e [R, k] and live [R] (all int32)
+void moe_lists(torch::Tensor topk_e, torch::Tensor live, torch::Tensor counts, torch::Tensor lists) {
+  TORCH_CHECK(topk_e.dim() == 2 && counts.dim() == 1, "moe_lists: topk_e [R, k], counts [E]");
+  const int64_t R = topk_e.size(0), k = topk_e.size(1), E = counts.size(0);
+  check_moe_dims(R, k, E, "moe_lists");
+  check_moe(topk_e, torch::kInt32, {R, k}, "moe_lists topk_e");
+  check_moe(live, torch::kInt32, {R}, "moe_lists live");
+  check_moe(counts, torch::kInt32, {E}, "moe_lists counts");
+  check_moe(lists, torch::kInt32, {E, R}, "moe_lists lists");
+  check(dsa_moe_lists(topk_e.data_ptr<int>(), live.data_ptr<int>(), counts.data_ptr<int>(), lists.data_ptr<int>(), (int)R,
+                      (int)k, (int)E, stream()),
+        "moe_lists");
+}
+
+// h bf16 [R, D], gate bf16 [E, D], live int32 [R] -> topk_e int32 [R, k], topk_w fp32 [R, k], counts, lists
+void moe_route(torch::Tensor h, torch::Tensor gate, torch::Tensor live, torch::Tensor topk_e, torch::Tensor topk_w,
+               torch::Tensor counts, torch::Tensor lists) {
+  TORCH_CHECK(h.dim() == 2 && gate.dim() == 2 && topk_e.dim() == 2, "moe_route: h [R, D], gate [E, D], topk_e [R, k]");
+  const int64_t R = h.size(0), D = h.size(1), E = gate.size(0), k = topk_e.size(1);
+  check_moe_dims(R, k, E, "moe_route");
+  TORCH_CHECK(D >= 8 && D % 8 == 0 && D <= INT_MAX, "moe_route: hidden size % 8 == 0");
+  check_moe_rows(h, D, "moe_route h");
+  check_moe(gate, torch::kBFloat16, {E, D}, "moe_route gate");
+  check_moe(live, torch::kInt32, {R}, "moe_route live");
+  check_moe(topk_e, torch::kInt32, {R, k}, "moe_route topk_e");
+  check_moe(topk_w, torch::kFloat32, {R, k}, "moe_route topk_w");
+  check_moe(counts, torch::kInt32, {E}, "moe_route counts");
+  check_moe(lists, torch::kInt32, {E, R}, "moe_route lists");
+  check(dsa_moe_route(h.data_ptr(), h.stride(0), gate.data_ptr(), live.data_ptr<int>(), topk_e.data_ptr<int>(),
+                      topk_w.data_ptr<float>(), counts.data_ptr<int>(), lists.data_ptr<int>(), (int)R, (int)k, (int)E,
+                      (int)D, stream()),
+        "moe_route");
+}
+
+// part[s][p][:] = x[p / src_div] W[expert(p)]^T over K slice s: x bf16 [R k / src_div, K], W bf16 [E, N, K],
+// counts [E], lists [E, R], part fp32 [S, R k, N]
+void moe_gemm(torch::Tensor x, int64_t src_div, torch::Tensor W, torch::Tensor counts, torch::Tensor lists,
+              torch::Tensor part) {
+  TORCH_CHECK(x.dim() == 2 && W.dim() == 3 && lists.dim() == 2 && part.dim() == 3,
+              "moe_gemm: x [rows, K], W [E, N, K], lists [E, R], part [S, R k, N]");
+  const int64_t E = W.size(0), N = W.size(1), K = W.size(2), R = lists.size(1), S = part.size(0), P = part.size(1);
+  TORCH_CHECK(R >= 1 && P % R == 0, "moe_gemm: part holds R k rows per K slice");
+  const int64_t k = P / R;
+  check_moe_dims(R, k, E, "moe_gemm");
+  TORCH_CHECK(moe_gemm_supported(R, N, K), "moe_gemm: 1 <= R <= 256, N % 256 == 0, K % 512 == 0");
+  TORCH_CHECK(S >= 1 && K % (512 * S) == 0, "moe_gemm: K slices of whole 512-element groups");
+  TORCH_CHECK((src_div == 1 || src_div == k) && x.size(0) * src_div == P,
+              "moe_gemm: x has a row per pair (src_div 1) or per token row (src_div k)");
+  check_moe_rows(x, K, "moe_gemm x");
+  check_moe(W, torch::kBFloat16, {E, N, K}, "moe_gemm W");
+  check_moe(counts, torch::kInt32, {E}, "moe_gemm counts");
+  check_moe(lists, torch::kInt32, {E, R}, "moe_gemm lists");
+  check_moe(part, torch::kFloat32, {S, P, N}, "moe_gemm part");
+  check(dsa_moe_gemm(x.data_ptr(), x.stride(0), (int)x.size(0), (int)src_div, W.data_ptr(), counts.data_ptr<int>(),
+                     lists.data_ptr<int>(), part.data_ptr<float>(), (int)R, (int)k, (int)E, (int)N, (int)K, (int)S,
+                     stream()),
+        "moe_gemm");
+}
+
+// a[p] = bf16(silu(g) u) from part fp32 [S, R k, 2F] for the pairs of live rows: a bf16 [R k, F]
+void moe_swiglu(torch::Tensor part, torch::Tensor live, torch::Tensor a) {
+  TORCH_CHECK(part.dim() == 3 && live.dim() == 1 && part.size(1) % live.size(0) == 0 && part.size(2) % 8 == 0,
+              "moe_swiglu: part [S, R k, 2F], live [R]");
+  const int64_t S = part.size(0), P = part.size(1), F = part.size(2) / 2, R = live.size(0);
+  check_moe_dims(R, P / R, P / R, "moe_swiglu");
+  check_moe(part, torch::kFloat32, {S, P, 2 * F}, "moe_swiglu part");
+  check_moe(live, torch::kInt32, {R}, "moe_swiglu live");
+  check_moe(a, torch::kBFloat16, {P, F}, "moe_swiglu a");
+  check(dsa_moe_swiglu(part.data_ptr<float>(), live.data_ptr<int>(), a.data_ptr(), (int)R, (int)(P / R), (int)F, (int)S,
+                       stream()),
+        "moe_swiglu");
+}
+
+// y[row] = bf16(sum_j topk_w[row][j] sum_s part[s][row k + j]) for live rows, zeros for the others
+void moe_combine(torch::Tensor part, torch::Tensor topk_w, torch::Tensor live, torch::Tensor y) {
+  TORCH_CHECK(part.dim() == 3 && topk_w.dim() == 2 && part.size(2) % 4 == 0, "moe_combine: part [S, R k, N], topk_w [R, k]");
+  const int64_t S = part.size(0), P = part.size(1), N = part.size(2), R = topk_w.size(0), k = topk_w.size(1);
+  check_moe_dims(R, k, k, "moe_combine");
+  check_moe(part, torch::kFloat32, {S, R * k, N}, "moe_combine part");
+  check_moe(topk_w, torch::kFloat32, {R, k}, "moe_combine topk_w");
+  check_moe(live, torch::kInt32, {R}, "moe_combine live");
+  check_moe(y, torch::kBFloat16, {R, N}, "moe_combine y");
+  check(dsa_moe_combine(part.data_ptr<float>(), topk_w.data_ptr<float>(), live.data_ptr<int>(), y.data_ptr(), N, (int)R,
+                        (int)k, (int)N, (int)S, stream()),
+        "moe_combine");
+}
+
 // out[M][N] (+)= a[K][M]^T b[K][N]  (csrc/gemm_nt.hip KM form: dW = dY^T X, token-major operands);
 // mode 2 = timing-only
 void gemm_km(torch::Tensor a, torch::Tensor b, torch::Tensor out, int64_t mode) {
@@ -1392,6 +1512,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "K slices w4_gemm runs this shape with (0: unsupported)");
   m.def("w4_dequant", &w4_dequant, pybind11::arg("codes"), pybind11::arg("zeros"), pybind11::arg("scales"),
         pybind11::arg("N"), pybind11::arg("K"), pybind11::arg("g"), pybind11::arg("out"));
+  m.def("moe_route", &moe_route, pybind11::arg("h"), pybind11::arg("gate"), pybind11::arg("live"),
+        pybind11::arg("topk_e"), pybind11::arg("topk_w"), pybind11::arg("counts"), pybind11::arg("lists"));
+  m.def("moe_lists", &moe_lists, pybind11::arg("topk_e"), pybind11::arg("live"), pybind11::arg("counts"),
+        pybind11::arg("lists"));
+  m.def("moe_gemm", &moe_gemm, pybind11::arg("x"), pybind11::arg("src_div"), pybind11::arg("W"), pybind11::arg("counts"),
+        pybind11::arg("lists"), pybind11::arg("part"));
+  m.def("moe_swiglu", &moe_swiglu, pybind11::arg("part"), pybind11::arg("live"), pybind11::arg("a"));
+  m.def("moe_combine", &moe_combine, pybind11::arg("part"), pybind11::arg("topk_w"), pybind11::arg("live"),
+        pybind11::arg("y"));
+  m.def("moe_gemm_supported", &moe_gemm_supported);
+  m.def("moe_gemm_form", [](int64_t R) { return dsa_moe_gemm_form((int)R); },
+        "16-token blocks of the moe_gemm form that runs R rows (1, 2, 4, 8 or 16)");
+  m.def("moe_gemm_split",
+        [](int64_t R, int64_t k, int64_t E, int64_t N, int64_t K) {
+          return dsa_moe_gemm_split((int)R, (int)k, (int)E, (int)N, (int)K);
+        },
+        "K slices the MoE MLP runs this shape with (0: unsupported)");
   m.def("swiglu_quant_fp8_rows", &swiglu_quant_fp8_rows, py::arg("gu"), py::arg("rs") = py::none(),
         py::arg("cs") = py::none());
   m.def("scale_rows_cols_", &scale_rows_cols_);

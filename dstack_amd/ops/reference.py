@@ -240,3 +240,63 @@ def adamw_(
     denom = (v / bc2).sqrt_().add_(eps)
     master.addcdiv_(m, denom, value=-lr / bc1)
     param.copy_(master.to(param.dtype))
+
+
+# ----------------------------------------------------------------------------------------------
+# Sparse mixture of experts (Mixtral): a linear router picks k of E experts per token
+# ----------------------------------------------------------------------------------------------
+def moe_topk(logits: torch.Tensor, k: int):
+    """Mixtral's routing rule on fp32 ``logits`` [R, E]: softmax over all E experts, the k largest (a
+    tie goes to the lower expert index, a NaN logit ranks below every number), their probabilities
+    divided by their sum.  Returns ``topk_e`` int32 [R, k] and ``topk_w`` fp32 [R, k]."""
+    logits = logits.float()
+    p = torch.softmax(logits, dim=-1)
+    key = torch.where(torch.isnan(logits), torch.full_like(logits, float("-inf")), logits)
+    topk_e = torch.sort(-key, dim=-1, stable=True).indices[:, :k]
+    w = torch.gather(p, 1, topk_e)
+    return topk_e.to(torch.int32), w / w.sum(-1, keepdim=True)
+
+
+def moe_lists(topk_e: torch.Tensor, live: torch.Tensor, E: int):
+    """``counts`` int32 [E] and ``lists`` int32 [E, R]: the pairs ``p = row * k + j`` of the rows with
+    ``live > 0`` that are routed to each expert, ascending; the tail of a list is -1."""
+    R, k = topk_e.shape
+    counts = torch.zeros(E, dtype=torch.int32, device=topk_e.device)
+    lists = torch.full((E, R), -1, dtype=torch.int32, device=topk_e.device)
+    flat = torch.where((live > 0)[:, None], topk_e, torch.full_like(topk_e, -1)).flatten()
+    for e in range(E):
+        pairs = torch.nonzero(flat == e).flatten()[:R]
+        counts[e] = pairs.numel()
+        lists[e, : pairs.numel()] = pairs.to(torch.int32)
+    return counts, lists
+
+
+def moe_route(h: torch.Tensor, gate: torch.Tensor, live: torch.Tensor, k: int):
+    """Router of a MoE layer: logits ``h @ gate^T`` in fp32 (accumulated in fp64, as the engine's CPU
+    GEMMs are), then :func:`moe_topk` and :func:`moe_lists`.  Returns ``(topk_e, topk_w, counts, lists)``."""
+    logits = (h.double() @ gate.double().t()).float()
+    topk_e, topk_w = moe_topk(logits, k)
+    return (topk_e, topk_w, *moe_lists(topk_e, live, gate.shape[0]))
+
+
+def moe_mlp(h: torch.Tensor, router: torch.Tensor, wgu: torch.Tensor, wdown: torch.Tensor, k: int,
+            live: torch.Tensor | None = None) -> torch.Tensor:
+    """The MoE MLP of ``h`` [R, D]: ``router`` [E, D], ``wgu`` [E, 2F, D] (gate rows first), ``wdown``
+    [E, D, F].  A plain loop over the experts; every product is accumulated in fp64 and rounded to
+    ``h``'s dtype where the dense MLP rounds (gate/up, SwiGLU), the weighted sum over a row's experts
+    is taken in fp64 and rounded once -- so a row's result does not depend on the other rows.  Rows
+    with ``live <= 0`` come out as zeros."""
+    R, E = h.shape[0], router.shape[0]
+    if live is None:
+        live = torch.ones(R, dtype=torch.int32, device=h.device)
+    _, topk_w, counts, lists = moe_route(h, router, live, k)
+    y = torch.zeros(R, wdown.shape[1], dtype=torch.float64, device=h.device)
+    for e in range(E):
+        pairs = lists[e, : int(counts[e])].long()
+        if not pairs.numel():
+            continue
+        rows = pairs // k
+        g, u = (h[rows].double() @ wgu[e].double().t()).to(h.dtype).double().chunk(2, dim=-1)
+        a = (F.silu(g) * u).to(h.dtype)
+        y[rows] += topk_w.flatten()[pairs].double()[:, None] * (a.double() @ wdown[e].double().t())
+    return y.to(h.dtype)

@@ -873,3 +873,188 @@ def w4_unshuffle(codes: torch.Tensor, zeros: torch.Tensor, scales: torch.Tensor,
     if K is not None and K != Kp:
         c, z, s = c[:, : K // 2].contiguous(), z[:, : K // g].contiguous(), s[:, : K // g].contiguous()
     return c, z, s
+
+
+# ----------------------------------------------------------------------------------------------
+# Sparse mixture-of-experts MLP of the decode step: csrc/moe.hip
+# ----------------------------------------------------------------------------------------------
+MOE_MAX_ROWS = 256  # token rows the kernels take (a decode batch or a verify step)
+MOE_MAX_EXPERTS = 64
+MOE_MAX_TOPK = 8
+
+
+def moe_check(E: int, k: int):
+    if not (1 <= k <= MOE_MAX_TOPK and k <= E <= MOE_MAX_EXPERTS):
+        raise ValueError(f"mixture of experts: {E} experts, {k} per token (num_local_experts: at most "
+                         f"{MOE_MAX_EXPERTS}; num_experts_per_tok: at most {MOE_MAX_TOPK} and no more than the experts)")
+
+
+def moe_route(h: torch.Tensor, gate: torch.Tensor, live: torch.Tensor, k: int, out=None):
+    """Router of a MoE layer for ``h`` [R, D] (R <= 256), ``gate`` [E, D], ``live`` int32 [R] (rows with
+    ``live <= 0`` get no pairs): ``topk_e`` int32 [R, k], ``topk_w`` fp32 [R, k] (Mixtral's rule:
+    ``ops.reference.moe_topk``), ``counts`` int32 [E] and ``lists`` int32 [E, R] (the pairs
+    ``row * k + j`` of each expert, ascending, then -1).  ``out``: the four tensors to write."""
+    if not _ext.use_hip(h):
+        return moe_route_ref(h, gate, live, k)
+    R, E = h.shape[0], gate.shape[0]
+    moe_check(E, k)
+    if out is None:
+        i32 = dict(dtype=torch.int32, device=h.device)
+        out = (torch.empty(R, k, **i32), torch.empty(R, k, dtype=torch.float32, device=h.device),
+               torch.empty(E, **i32), torch.empty(E, R, **i32))
+    _ext.require().moe_route(h, gate, live, *out)
+    return out
+
+
+def moe_route_ref(h, gate, live, k):
+    from dstack_amd.ops import reference as ref
+
+    return ref.moe_route(h, gate, live, k)
+
+
+def moe_lists(topk_e: torch.Tensor, live: torch.Tensor, E: int, out=None):
+    """``(counts, lists)`` of :func:`moe_route` for a given ``topk_e`` int32 [R, k]."""
+    if not _ext.use_hip(topk_e):
+        from dstack_amd.ops import reference as ref
+
+        return ref.moe_lists(topk_e, live, E)
+    if out is None:
+        out = (torch.empty(E, dtype=torch.int32, device=topk_e.device),
+               torch.empty(E, topk_e.shape[0], dtype=torch.int32, device=topk_e.device))
+    _ext.require().moe_lists(topk_e, live, *out)
+    return out
+
+
+def moe_gemm_split(R: int, k: int, E: int, N: int, K: int) -> int:
+    """K slices the grouped GEMM runs a shape with, from the shape alone (0: unsupported on the kernel)."""
+    return int(_ext.require().moe_gemm_split(R, k, E, N, K))
+
+
+def moe_gemm(x: torch.Tensor, src_div: int, W: torch.Tensor, counts: torch.Tensor, lists: torch.Tensor, split: int,
+             part: torch.Tensor | None = None) -> torch.Tensor:
+    """Grouped GEMM over the routed pairs: ``part[s, p] = x[p // src_div] @ W[expert(p)]^T`` over K
+    slice ``s`` of ``split``, fp32 [split, R k, N], for the pairs in ``lists`` (other rows of ``part``
+    are not written).  ``x`` bf16 [R, K] with ``src_div = k`` (every pair of a row reads the row) or
+    [R k, K] with ``src_div = 1``; ``W`` bf16 [E, N, K], N % 256 == 0, K % (512 split) == 0."""
+    P = x.shape[0] * src_div
+    if not _ext.use_hip(x):
+        return moe_gemm_ref(x, src_div, W, counts, lists, split)
+    if part is None:
+        part = torch.empty(split, P, W.shape[1], dtype=torch.float32, device=x.device)
+    _ext.require().moe_gemm(x, src_div, W, counts, lists, part)
+    return part
+
+
+def moe_gemm_ref(x, src_div, W, counts, lists, split):
+    """Reference of :func:`moe_gemm`: every slice accumulated in fp64; rows of no pair are zeros."""
+    E, N, K = W.shape
+    P, ks = x.shape[0] * src_div, K // split
+    part = torch.zeros(split, P, N, dtype=torch.float32, device=x.device)
+    for e in range(E):
+        pairs = lists[e, : int(counts[e])].long()
+        for s in range(split):
+            sl = slice(s * ks, (s + 1) * ks)
+            part[s, pairs] = (x[pairs // src_div][:, sl].double() @ W[e][:, sl].double().t()).float()
+    return part
+
+
+def moe_swiglu(part: torch.Tensor, live: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """``a[p] = dtype(silu(g) * u)`` with ``g, u`` the halves of ``sum_s part[s, p]`` (fp32, added in the
+    order s = 0, 1, ..; one rounding), for the pairs of rows with ``live > 0``: bf16 [R k, F] from
+    ``part`` fp32 [S, R k, 2F].  Other rows of ``a`` are not written."""
+    P, F2 = part.shape[1], part.shape[2]
+    if out is None:
+        out = torch.zeros(P, F2 // 2, dtype=torch.bfloat16, device=part.device)
+    if _ext.use_hip(part):
+        _ext.require().moe_swiglu(part, live, out)
+        return out
+    rows = (live > 0).repeat_interleave(P // live.shape[0])
+    g, u = part.sum(0)[rows].chunk(2, dim=-1)
+    out[rows] = (torch.nn.functional.silu(g) * u).to(out.dtype)
+    return out
+
+
+def moe_combine(part: torch.Tensor, topk_w: torch.Tensor, live: torch.Tensor,
+                out: torch.Tensor | None = None) -> torch.Tensor:
+    """``y[row] = dtype(sum_j topk_w[row, j] * sum_s part[s, row k + j])`` in fp32, in the order j = 0,
+    1, .. (one rounding), zeros for the rows with ``live <= 0`` (their partials are not read): bf16
+    [R, N] from ``part`` fp32 [S, R k, N]."""
+    R, k = topk_w.shape
+    if out is None:
+        out = torch.empty(R, part.shape[2], dtype=torch.bfloat16, device=part.device)
+    if _ext.use_hip(part):
+        _ext.require().moe_combine(part, topk_w, live, out)
+        return out
+    d = torch.where((live > 0)[:, None, None], part.sum(0).view(R, k, -1), torch.zeros((), device=part.device))
+    out.copy_((d * topk_w[:, :, None]).sum(1))
+    return out
+
+
+class MoeWorkspace:
+    """The buffers of :func:`moe_mlp` for up to 256 rows of one model shape, allocated once (a captured
+    graph holds their addresses): routing, the fp32 split-K partials of the larger of the two GEMMs
+    at its largest row count, and the per-pair activations."""
+
+    def __init__(self, E: int, k: int, D: int, F: int, device):
+        moe_check(E, k)
+        C = _ext.require()
+        if not (C.moe_gemm_supported(MOE_MAX_ROWS, 2 * F, D) and C.moe_gemm_supported(MOE_MAX_ROWS, D, F)):
+            raise ValueError(f"mixture of experts: hidden size {D} and FFN size {F} must be multiples of 512 (the "
+                             "grouped decode GEMM's tiles)")
+        self.E, self.k, self.D, self.F = E, k, D, F
+        R = MOE_MAX_ROWS
+        self.split = {r: (C.moe_gemm_split(r, k, E, 2 * F, D), C.moe_gemm_split(r, k, E, D, F)) for r in range(1, R + 1)}
+        floats = max(max(s1 * r * k * 2 * F, s2 * r * k * D) for r, (s1, s2) in self.split.items())
+        i32 = dict(dtype=torch.int32, device=device)
+        self.topk_e, self.topk_w = torch.zeros(R * k, **i32), torch.zeros(R * k, dtype=torch.float32, device=device)
+        self.counts, self.lists = torch.zeros(E, **i32), torch.zeros(E * R, **i32)
+        self.part = torch.zeros(floats, dtype=torch.float32, device=device)
+        self.a = torch.zeros(R * k, F, dtype=torch.bfloat16, device=device)
+
+    def nbytes(self) -> int:
+        return self.part.numel() * 4 + self.a.numel() * 2
+
+
+def moe_mlp(h: torch.Tensor, router: torch.Tensor, wgu: torch.Tensor, wdown: torch.Tensor, k: int, live: torch.Tensor,
+            ws: MoeWorkspace) -> torch.Tensor:
+    """The MoE MLP of up to 256 rows on the kernels: route, grouped gate/up GEMM over the layer input,
+    reduce + SwiGLU, grouped down GEMM over the per-pair activations, reduce + weighted sum.  No host
+    read, nothing allocated but the result: capturable.  ``ws``: :class:`MoeWorkspace`."""
+    R, E, D, F = h.shape[0], router.shape[0], ws.D, ws.F
+    if h.stride(-1) != 1 or h.stride(0) % 8 or h.data_ptr() % 16:
+        h = h.contiguous()
+    s1, s2 = ws.split[R]
+    P = R * k
+    topk_e, topk_w, counts, lists = moe_route(
+        h, router, live, k, out=(ws.topk_e[:P].view(R, k), ws.topk_w[:P].view(R, k), ws.counts, ws.lists[: E * R].view(E, R)))
+    part = moe_gemm(h, k, wgu, counts, lists, s1, part=ws.part[: s1 * P * 2 * F].view(s1, P, 2 * F))
+    a = moe_swiglu(part, live, out=ws.a[:P])
+    part = moe_gemm(a, 1, wdown, counts, lists, s2, part=ws.part[: s2 * P * D].view(s2, P, D))
+    return moe_combine(part, topk_w, live)
+
+
+def moe_mlp_eager(h: torch.Tensor, router: torch.Tensor, wgu: torch.Tensor, wdown: torch.Tensor, k: int,
+                  live: torch.Tensor | None = None) -> torch.Tensor:
+    """The MoE MLP of any number of rows on library GEMMs (prefill): the pairs sorted by expert, one
+    GEMM pair per non-empty expert, the weighted sum in fp32 and rounded once.  Reads the counts on the
+    host once, so it cannot be captured."""
+    from dstack_amd.ops import reference as ref
+
+    R, E = h.shape[0], router.shape[0]
+    topk_e, topk_w = ref.moe_topk(h.float() @ router.float().t(), k)
+    flat = topk_e.flatten().long()
+    if live is not None:
+        flat = torch.where((live > 0).repeat_interleave(k), flat, torch.full_like(flat, E))
+    order = torch.argsort(flat, stable=True)
+    counts = torch.bincount(flat, minlength=E + 1).tolist()
+    y = torch.zeros(R, wdown.shape[1], dtype=torch.float32, device=h.device)
+    wflat, start = topk_w.flatten(), 0
+    for e in range(E):
+        pairs, start = order[start : start + counts[e]], start + counts[e]
+        if not counts[e]:
+            continue
+        rows = pairs // k
+        gu = h[rows] @ wgu[e].t()
+        a = _ext.require().swiglu_fwd(gu) if _ext.use_hip(gu) else ref.swiglu(gu)
+        y.index_add_(0, rows, (a @ wdown[e].t()).float() * wflat[pairs][:, None])
+    return y.to(h.dtype)

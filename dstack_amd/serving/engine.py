@@ -33,7 +33,7 @@ import torch
 import torch.distributed as dist
 
 from dstack_amd.ops import serving as sops
-from dstack_amd.serving.model import ServingLlama, check_awq, load_spec
+from dstack_amd.serving.model import ServingLlama, check_awq, check_moe, load_spec
 
 
 @dataclass
@@ -210,6 +210,7 @@ class LLMEngine:
         if quantization == "mxfp4" and tp_group is not None:
             raise ValueError("quantization=\"mxfp4\" is not supported with tensor parallel yet")
         spec = load_spec(model)
+        check_moe(spec, quantization, tp_group is not None, kw.get("lora_modules"))  # before any weight is loaded
         if spec.awq is not None or quantization == "awq":  # an AWQ checkpoint selects the mode by itself
             check_awq(spec, quantization)
             quantization = "awq"

@@ -206,19 +206,32 @@ class ModelSpec:
     family: str = "llama"  # llama | mistral | qwen2 (same block; qwen2 adds q/k/v biases)
     qkv_bias: bool = False
     awq: AwqConfig | None = None  # the checkpoint's projections are AWQ 4-bit (config.json quantization_config)
+    n_experts: int = 0  # mixtral: experts per layer in place of the dense MLP (0: dense)
+    experts_per_tok: int = 0  # mixtral: experts the router picks per token
+
+
+# sparse-MoE architectures with random weights (benchmarks): (block config, experts, experts per token)
+MOE_CONFIGS = {
+    "mixtral-8x7b": (LlamaConfig(name="mixtral-8x7b", dim=4096, n_layers=32, n_heads=32, n_kv_heads=8, ffn_dim=14336,
+                                 vocab_size=32000, rope_theta=1e6, norm_eps=1e-5, max_seq_len=32768), 8, 2),
+}
 
 
 def load_spec(model: str) -> ModelSpec:
     """``model`` is a built-in config name (``llama-3-8b``, ``llama-3-70b``, …: random weights) or an
     HF checkpoint directory (``config.json`` + ``*.safetensors``) of the Llama block family: Llama
-    2/3/3.x, Mistral (sliding-window models are served up to their window) and Qwen2 / Qwen2.5
-    (q/k/v projection biases).  A checkpoint whose ``config.json`` has a ``quantization_config`` must be
+    2/3/3.x, Mistral (sliding-window models are served up to their window), Qwen2 / Qwen2.5
+    (q/k/v projection biases) and Mixtral (the Mistral block with ``num_local_experts`` experts behind a
+    router that picks ``num_experts_per_tok`` per token; ``mixtral-8x7b`` is built in).  A checkpoint whose ``config.json`` has a ``quantization_config`` must be
     an AutoAWQ 4-bit "GEMM" one (``ModelSpec.awq``); anything else in it is an error naming the field."""
     if model in CONFIGS:
         return ModelSpec(CONFIGS[model], eos_token_ids=())
+    if model in MOE_CONFIGS:
+        cfg, n_experts, per_tok = MOE_CONFIGS[model]
+        return ModelSpec(cfg, eos_token_ids=(), family="mixtral", n_experts=n_experts, experts_per_tok=per_tok)
     cfg_path = os.path.join(model, "config.json")
     if not os.path.exists(cfg_path):
-        raise ValueError(f"unknown model {model!r}: neither a built-in config ({', '.join(CONFIGS)}) "
+        raise ValueError(f"unknown model {model!r}: neither a built-in config ({', '.join([*CONFIGS, *MOE_CONFIGS])}) "
                          "nor a directory with config.json")
     with open(cfg_path) as f:
         hf = json.load(f)
@@ -238,7 +251,7 @@ def load_spec(model: str) -> ModelSpec:
     # sliding-window attention (Mistral v0.1, Qwen2 with use_sliding_window): up to the window it is
     # full causal attention, so such a model is served with max_model_len <= window
     window = hf.get("sliding_window")
-    if window and (family == "mistral" or hf.get("use_sliding_window")):
+    if window and (family in ("mistral", "mixtral") or hf.get("use_sliding_window")):
         max_len = min(max_len, int(window))
     if hf.get("hidden_act", "silu") != "silu":
         raise ValueError(f"unsupported activation {hf.get('hidden_act')} (SwiGLU / silu only)")
@@ -261,11 +274,30 @@ def load_spec(model: str) -> ModelSpec:
     eos = hf.get("eos_token_id")
     eos_ids = tuple(eos) if isinstance(eos, list) else ((eos,) if eos is not None else ())
     awq = _awq_config(hf["quantization_config"]) if hf.get("quantization_config") else None
+    n_experts = per_tok = 0
+    if family == "mixtral":  # the Mistral block with the MLP replaced by experts behind a linear router
+        n_experts, per_tok = int(hf.get("num_local_experts", 8)), int(hf.get("num_experts_per_tok", 2))
+        sops.moe_check(n_experts, per_tok)
     return ModelSpec(cfg, scaling, bool(hf.get("tie_word_embeddings", False)), hf.get("bos_token_id"), eos_ids,
-                     path=model, family=family, qkv_bias=family == "qwen2", awq=awq)
+                     path=model, family=family, qkv_bias=family == "qwen2", awq=awq, n_experts=n_experts,
+                     experts_per_tok=per_tok)
 
 
-SUPPORTED_FAMILIES = ("llama", "mistral", "qwen2")
+SUPPORTED_FAMILIES = ("llama", "mistral", "qwen2", "mixtral")
+
+
+def check_moe(spec: ModelSpec, quantization: str | None, tensor_parallel: bool, lora_modules=None):
+    """What a mixture-of-experts model cannot be combined with yet, each named by its option."""
+    if not spec.n_experts:
+        return
+    sops.moe_check(spec.n_experts, spec.experts_per_tok)
+    if quantization is not None or spec.awq is not None:
+        raise ValueError(f"quantization={quantization or 'awq'!r} (--quantization) is not supported on a "
+                         "mixture-of-experts model: its experts are served in bf16")
+    if tensor_parallel:
+        raise ValueError("tensor parallel (tp_group) is not supported on a mixture-of-experts model: a replica is one GPU")
+    if lora_modules:
+        raise ValueError("lora_modules (--lora-modules) is not supported on a mixture-of-experts model")
 
 
 def check_awq(spec: ModelSpec, quantization: str | None):
@@ -290,6 +322,7 @@ class ServingLlama:
         if quantization not in (None, "fp8", "mxfp4", "awq"):
             raise ValueError(f"unsupported quantization {quantization!r} (supported: fp8, mxfp4, awq)")
         check_awq(spec, quantization)
+        check_moe(spec, quantization, tp_group is not None)
         if quantization in ("mxfp4", "awq") and tp_group is not None:
             raise ValueError(f"quantization=\"{quantization}\" is not supported with tensor parallel yet")
         if kv_cache_dtype not in ("auto", "fp8"):
@@ -319,6 +352,11 @@ class ServingLlama:
         self.hip = self.device.type == "cuda" and not _ext.force_torch()
         if self.hip:
             _ext.require()
+        # mixture of experts: E experts per layer, k per token; on the GPU up to 256 rows run on the
+        # kernels of csrc/moe.hip from one workspace (its constructor refuses shapes they do not cover)
+        self.E, self.topk = spec.n_experts, spec.experts_per_tok
+        self.moe_ws = sops.MoeWorkspace(self.E, self.topk, cfg.dim, cfg.ffn_dim, self.device) if self.E and self.hip else None
+        self._moe_live = None  # int32 [rows] of the running step: > 0 where the row holds a token
         # DSTACK_AMD_GEMV=0: small decode batches on hipBLASLt too (A/B switch)
         self.gemv = os.environ.get("DSTACK_AMD_GEMV", "1") != "0"
         # decode-batch fp8 projections (5..256 rows) on the in-tree fp8 GEMM (csrc/fp8_gemm.hip)
@@ -367,6 +405,13 @@ class ServingLlama:
             self.lm_head = self._empty(self.V, d)
         if self.spec.awq is not None:  # the projections arrive 4-bit (load_hf): no bf16 copy is ever made
             self.layers = [dict(attn_norm=self._empty(d), ffn_norm=self._empty(d)) for _ in range(cfg.n_layers)]
+        elif self.E:  # experts in place of the dense MLP: the one copy both the kernels and the eager path read
+            self.layers = [
+                dict(attn_norm=self._empty(d), wqkv=self._empty(self.NH * hd, d), wo=self._empty(d, self.H * hd),
+                     ffn_norm=self._empty(d), wgu=self._empty(self.E, 2 * self.F, d), wdown=self._empty(self.E, d, self.F),
+                     router=self._empty(self.E, d))
+                for _ in range(cfg.n_layers)
+            ]
         else:
             self.layers = [
                 dict(attn_norm=self._empty(d), wqkv=self._empty(self.NH * hd, d), wo=self._empty(d, self.H * hd),
@@ -416,9 +461,16 @@ class ServingLlama:
             full = draw(f"{i}.wqkv", ((cfg.n_heads + 2 * cfg.n_kv_heads) * hd, cfg.dim), std)
             q, k, v = full.split([cfg.n_heads * hd, cfg.n_kv_heads * hd, cfg.n_kv_heads * hd])
             L["wqkv"].copy_(torch.cat([self._shard("q", q), self._shard("k", k), self._shard("v", v)]))
+            L["wo"].copy_(self._shard("wo", draw(f"{i}.wo", (cfg.dim, cfg.n_heads * hd), out_std)))
+            if self.E:  # (one rank: check_moe)
+                L["router"].copy_(draw(f"{i}.router", (self.E, cfg.dim), std))
+                for e in range(self.E):
+                    L["wgu"][e].copy_(draw(f"{i}.wgu.{e}", (2 * cfg.ffn_dim, cfg.dim), std))
+                    L["wdown"][e].copy_(draw(f"{i}.wdown.{e}", (cfg.dim, cfg.ffn_dim), out_std))
+                del full, q, k, v
+                continue
             full = draw(f"{i}.wgu", (2 * cfg.ffn_dim, cfg.dim), std)
             L["wgu"].copy_(torch.cat([self._shard("gate", full[: cfg.ffn_dim]), self._shard("up", full[cfg.ffn_dim :])]))
-            L["wo"].copy_(self._shard("wo", draw(f"{i}.wo", (cfg.dim, cfg.n_heads * hd), out_std)))
             L["wdown"].copy_(self._shard("wdown", draw(f"{i}.wdown", (cfg.dim, cfg.ffn_dim), out_std)))
             if self.spec.qkv_bias:
                 b = draw(f"{i}.bqkv", ((cfg.n_heads + 2 * cfg.n_kv_heads) * hd,), std)
@@ -495,6 +547,23 @@ class ServingLlama:
                             kind = key.split(".")[1][0]
                             lo = {"q": 0, "k": H * hd, "v": (H + KVH) * hd}[kind]
                             put(L["bqkv"][lo : lo + (H if kind == "q" else KVH) * hd], t, kind)
+                        elif self.E and key in ("block_sparse_moe.gate.weight", "mlp.gate.weight"):
+                            put(L["router"], t)
+                        elif self.E and len(parts) == 8 and parts[3:5] == ["block_sparse_moe", "experts"] \
+                                and parts[5].isdigit() and int(parts[5]) < self.E and parts[6] in ("w1", "w2", "w3") \
+                                and parts[7] == "weight":
+                            # the Hub's spelling: per expert w1 (gate) [F, D], w3 (up) [F, D], w2 (down) [D, F]
+                            e = int(parts[5])
+                            put({"w1": L["wgu"][e, :f], "w3": L["wgu"][e, f:], "w2": L["wdown"][e]}[parts[6]], t)
+                        elif self.E and key in ("mlp.experts.gate_up_proj", "mlp.experts.down_proj"):
+                            # the fused spelling: [E, 2F, D] (gate rows first) and [E, D, F]; expert by expert
+                            dst = L["wgu"] if key.endswith("gate_up_proj") else L["wdown"]
+                            if tuple(t.shape) != tuple(dst.shape):
+                                raise ValueError(f"{name}: expected {list(dst.shape)}, got {list(t.shape)}")
+                            for e in range(self.E):
+                                put(dst[e], t[e])
+                        elif self.E and key.startswith("mlp."):
+                            raise ValueError(f"unexpected tensor {name}")
                         elif key == "mlp.gate_proj.weight":
                             put(L["wgu"][:f], t, "gate")
                         elif key == "mlp.up_proj.weight":
@@ -510,8 +579,14 @@ class ServingLlama:
             expected.add("lm_head.weight")
         for i in range(self.cfg.n_layers):
             expected |= {f"model.layers.{i}.{k}.weight" for k in ("input_layernorm", "post_attention_layernorm")}
-            expected |= {f"model.layers.{i}.{k}.{kind}" for k in self.AWQ_PROJ
+            expected |= {f"model.layers.{i}.{k}.{kind}" for k in self.AWQ_PROJ if not (self.E and k.startswith("mlp."))
                          for kind in (self.AWQ_KINDS if awq else ("weight",))}
+            if self.E and any(".block_sparse_moe." in n for n in seen):  # the Hub's per-expert tensors
+                pre = f"model.layers.{i}.block_sparse_moe"
+                expected |= {f"{pre}.gate.weight"} | {f"{pre}.experts.{e}.{w}.weight" for e in range(self.E)
+                                                      for w in ("w1", "w2", "w3")}
+            elif self.E:  # the fused tensors
+                expected |= {f"model.layers.{i}.mlp.{k}" for k in ("gate.weight", "experts.gate_up_proj", "experts.down_proj")}
             if self.spec.qkv_bias:
                 expected |= {f"model.layers.{i}.self_attn.{p}_proj.bias" for p in "qkv"}
         missing = expected - seen
@@ -706,6 +781,7 @@ class ServingLlama:
         padded ``max_rank``.  Call before the KV cache is sized."""
         from dstack_amd.serving.lora import padded_rank
 
+        check_moe(self.spec, None, False, lora_modules=True)
         if self.quantization == "fp8":
             raise ValueError("LoRA adapters are not supported with quantization=\"fp8\": the fp8 projections take "
                              "e4m3 inputs and hand on unscaled outputs, so an adapter has neither a bf16 input "
@@ -1012,6 +1088,9 @@ class ServingLlama:
         """(x + o @ wo^T) -> norm -> SwiGLU MLP; returns (new residual, mlp output).  ``lora`` (see
         ``_lora_add``): layer ``li``'s adapters are added to the o, gate/up and down products."""
         wo = L["wo"]
+        if "router" in L:  # mixture of experts (bf16, one rank, no adapters: check_moe)
+            x, h = self._add_rms(x, self._mm(o, wo), L["ffn_norm"])
+            return x, self._moe_mlp(L, h)
         if lora is not None:  # (bf16 weights on one rank: enable_lora refuses fp8 and tensor parallel)
             ao = self._lora_add(li, "wo", o, self._mm(o, wo), lora)
             x, h = self._add_rms(x, ao, L["ffn_norm"])
@@ -1037,6 +1116,19 @@ class ServingLlama:
             return x, self._reduce(self._mm_fp8(Fp8Act(q, sc), wd, defer=mode))
         gu = self._mm(h, wgu)
         return x, self._reduce(self._mm(self._swiglu(gu), wd))
+
+    def _moe_mlp(self, L, h):
+        """The experts' MLP of ``h`` [rows, dim]; ``self._moe_live`` says which rows hold a token (the
+        others come out as zeros).  GPU: up to 256 rows (a decode batch, a verify step, a short
+        prefill) on the kernels of ``csrc/moe.hip`` -- no host read, so the step can be captured; more
+        rows (prefill) on one library GEMM pair per non-empty expert (``sops.moe_mlp_eager``), which
+        reads the routing counts on the host once per layer.  CPU: ``ref.moe_mlp`` for every row
+        count.  All three read the same ``wgu`` [E, 2F, D] and ``wdown`` [E, D, F]."""
+        if not self.hip:
+            return ref.moe_mlp(h, L["router"], L["wgu"], L["wdown"], self.topk, self._moe_live)
+        if h.shape[0] <= sops.MOE_MAX_ROWS:
+            return sops.moe_mlp(h, L["router"], L["wgu"], L["wdown"], self.topk, self._moe_live, self.moe_ws)
+        return sops.moe_mlp_eager(h, L["router"], L["wgu"], L["wdown"], self.topk, self._moe_live)
 
     @staticmethod
     def _rows(h) -> int:
@@ -1073,6 +1165,8 @@ class ServingLlama:
             lora = self._lora_runs(lora_idx, rows) or None
         x = F.embedding(tokens, self.embed)
         delta = None
+        if self.E:  # padding rows (slot -1) are routed to no expert
+            self._moe_live = (slots + 1).to(torch.int32)
         bounds = []
         for i in range(len(lens)):
             nxt = offsets[i + 1] if i + 1 < len(lens) else rows
@@ -1180,6 +1274,8 @@ class ServingLlama:
         H, KVH = self.H, self.KVH
         x = F.embedding(tokens, self.embed)
         delta = None
+        if self.E:  # a row without a cache slot (graph padding, an unused verify row) is inert
+            self._moe_live = (slots + 1).to(torch.int32)
         for li, L in enumerate(self.layers):
             if delta is None:
                 h = self._rms(x, L["attn_norm"], next_w=L["wqkv"])
