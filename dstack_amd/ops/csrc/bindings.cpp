@@ -339,7 +339,9 @@ std::vector<torch::Tensor> cross_entropy_fwd(torch::Tensor logits, torch::Tensor
 torch::Tensor cross_entropy_bwd(torch::Tensor logits, torch::Tensor target, torch::Tensor lse, torch::Tensor scale,
                                 bool inplace) {
   check_bf16(logits, "logits");
+  TORCH_CHECK(target.scalar_type() == torch::kInt64 && target.is_contiguous(), "target int64");
   const int rows = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V % 8 == 0, "vocab must be a multiple of 8");
   auto out = inplace ? logits : torch::empty_like(logits);
   check(dsa_ce_bwd(logits.data_ptr(), target.data_ptr<int64_t>(), lse.data_ptr<float>(), scale.data_ptr<float>(),
                    out.data_ptr(), rows, V, stream()),

@@ -419,6 +419,7 @@ __global__ __launch_bounds__(256) void rope_qkv_kernel(const bf16_t* __restrict_
 // Softmax cross-entropy over a [T, V] bf16 logits matrix. One 256-thread block per row.
 // fwd: online (max, sum-exp) per lane -> block combine -> lse, loss = lse - logit[target].
 // bwd: dlogit = scale * (exp(logit - lse) - onehot), written in place over the logits.
+// A row whose target is outside [0, V) (ignore_index) has loss 0 and a zero gradient row.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void online_merge(float& m, float& s, float m2, float s2) {
   const float mn = fmaxf(m, m2);
@@ -480,6 +481,12 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const bf16_t* __restrict__ 
   const bf16_t* L = logits + row * (size_t)V;
   bf16_t* G = dlogits + row * (size_t)V;
   const int nch = V >> 3;
+  if (t < 0 || t >= V) {  // an ignored row (the forward gave it loss 0): no gradient (block-uniform)
+    const float z[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int ch = threadIdx.x; ch < nch; ch += blockDim.x) *reinterpret_cast<us8*>(G + ch * 8) = pack8(z);
+    for (int i = (nch << 3) + threadIdx.x; i < V; i += blockDim.x) G[i] = f2bf(0.f);
+    return;
+  }
   for (int ch = threadIdx.x; ch < nch; ch += blockDim.x) {
     float v[8];
     unpack8(*reinterpret_cast<const us8*>(L + ch * 8), v);

@@ -577,18 +577,26 @@ def weight_grad(g: torch.Tensor, x: torch.Tensor, out: torch.Tensor, accumulate:
 
 
 class _CrossEntropy(torch.autograd.Function):
+    """Mean over the rows whose target lies in [0, V); any other target (``ignore_index`` -100) has
+    loss 0 and a zero gradient row, and all rows ignored gives loss 0.  The mean over all T rows is
+    rescaled by T / count (counted on the device, no host synchronisation): with no ignored row that
+    factor is exactly 1.0, so loss and gradients keep the bits of the plain mean."""
+
     @staticmethod
     def forward(ctx, logits, target):
         C = _ext.require()
         loss_rows, lse = C.cross_entropy_fwd(logits, target)
-        ctx.save_for_backward(logits, target, lse)
-        return loss_rows.mean()
+        T, V = logits.shape
+        count = ((target >= 0) & (target < V)).sum().clamp_(min=1)
+        ratio = count.new_full((), T) / count  # a true division of two device integers: T / T is 1.0
+        ctx.save_for_backward(logits, target, lse, ratio)
+        return loss_rows.mean() * ratio
 
     @staticmethod
     def backward(ctx, dloss):
         C = _ext.require()
-        logits, target, lse = ctx.saved_tensors
-        scale = dloss / logits.shape[0]
+        logits, target, lse, ratio = ctx.saved_tensors
+        scale = dloss / logits.shape[0] * ratio
         # gradient is written in place over the logits buffer (logits are dead after this)
         dlogits = C.cross_entropy_bwd(logits, target, lse, scale.float().reshape(1), True)
         return dlogits, None

@@ -85,8 +85,15 @@ def _process_job(s: Session, job_id):
         scheduler.wake(scheduler.TERMINATING_JOBS, scheduler.RUNS)
         return
     # ---- 1) reuse a pool instance ----
-    if _assign_pool_instance(s, run, job, spec, profile, fleet, multinode, master_jpd, volumes):
+    assigned = _assign_pool_instance(s, run, job, spec, profile, fleet, multinode, master_jpd, volumes)
+    if assigned:
         scheduler.wake(scheduler.RUNNING_JOBS, scheduler.RUNS)
+        return
+    if assigned is None:
+        # a matching instance is claimed by another reconciler right now (its health check): the job
+        # stays SUBMITTED for the next pass rather than failing for want of capacity
+        job.last_processed_at = get_current_datetime()
+        scheduler.wake_later(0.2, scheduler.SUBMITTED_JOBS)
         return
     if profile.creation_policy == CreationPolicy.REUSE:
         _no_capacity(job, "No idle instance matches the requirements (creation_policy: reuse)")
@@ -175,7 +182,9 @@ def _gpu_request(spec, offer: InstanceOfferWithAvailability) -> int:
 
 
 def _assign_pool_instance(s: Session, run: RunModel, job: JobModel, spec, profile, fleet, multinode: bool,
-                          master_jpd, volumes=()) -> bool:
+                          master_jpd, volumes=()) -> Optional[bool]:
+    """True: assigned.  False: no pool instance matches.  None: one matches but is claimed by another
+    reconciler at this moment."""
     instances = pools_services.list_project_instances(s, run.project)
     cands = pools_services.filter_pool_instances(instances, profile, spec.requirements, fleet=fleet,
                                                  multinode=multinode, master_jpd=master_jpd)
@@ -184,8 +193,10 @@ def _assign_pool_instance(s: Session, run: RunModel, job: JobModel, spec, profil
     if not cands:
         return False
     ls = lockset("instances")
+    claimed_elsewhere = False
     for inst, shared in cands:
         if not ls.try_add_many([inst.id]):
+            claimed_elsewhere = True
             continue
         assigned = False
         try:
@@ -222,7 +233,7 @@ def _assign_pool_instance(s: Session, run: RunModel, job: JobModel, spec, profil
                 release_at_transaction_end(s, ls, [inst.id])
             else:
                 ls.remove_many([inst.id])
-    return False
+    return None if claimed_elsewhere else False
 
 
 def _create_instance_for_job(s: Session, run: RunModel, job: JobModel, spec, offer, jpd: JobProvisioningData, profile,

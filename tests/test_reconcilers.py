@@ -246,6 +246,26 @@ def test_idle_pool_instance_reused_with_xgmi_gpus(db):
         assert len(inst.busy_gpus.split(",")) == 4
 
 
+def test_job_waits_for_an_idle_instance_claimed_by_another_reconciler(db):
+    """The only matching instance is held (the instances reconciler's health check): the job stays
+    SUBMITTED and is assigned on the next pass, not failed for want of capacity."""
+    from dstack_amd.server.background.tasks import process_submitted_jobs as psj
+    from dstack_amd.server.services.locking import lockset
+
+    with session_scope() as s:
+        iid = _instance(s, backend=BackendType.REMOTE)
+        rid = _submit(s, {"type": "task", "commands": ["x"], "resources": {"gpu": "MI355X:8"}})
+    with lockset("instances").hold([iid]), session_scope() as s:
+        psj._process_job(s, _job(s, rid).id)
+    with session_scope() as s:
+        j = _job(s, rid)
+        assert j.status == "submitted" and j.termination_reason is None and j.instance_id is None
+        psj._process_job(s, j.id)
+    with session_scope() as s:
+        j = _job(s, rid)
+        assert j.status == "provisioning" and j.instance_id == iid
+
+
 def test_retry_policy_resubmits_after_no_capacity(db):
     from dstack_amd.server.background.tasks import process_runs as pr
     from dstack_amd.server.background.tasks import process_submitted_jobs as psj
