@@ -32,7 +32,8 @@ hipError_t dsa_fa_bwd(const void*, const void*, const void*, const float*, void*
                       int, float, int, const float*, const float*, hipStream_t);
 int dsa_paged_page_size();
 hipError_t dsa_rope_cache_write(void*, const int*, const int*, const float*, const float*, void*, void*, int, int,
-                                int, int, float, float, const float*, const float*, hipStream_t);
+                                int, int, float, float, const float*, const float*, const float*, const float*, float,
+                                hipStream_t);
 hipError_t dsa_paged_decode(const void*, long, const void*, const void*, const int*, int, const int*, void*, float*,
                             float*, int, int, int, int, int, float, int, float, float, hipStream_t);
 hipError_t dsa_paged_verify(const void*, long, int, const void*, const void*, const int*, int, int, const int*,
@@ -1066,11 +1067,13 @@ bool check_cache(const torch::Tensor& k, const torch::Tensor& v, int64_t KVH) {
 
 // rotates q/k of qkv [T, (H+2KVH)*128] in place and writes k, v of each token to its cache slot;
 // rs [T] / cs [(H+2KVH)*128] (optional, together): qkv is a raw fp8 GEMM product whose row-wise
-// scales are applied first (and written back for every head)
+// scales are applied first (and written back for every head); q_norm / k_norm fp32 [128] (optional,
+// together): every q / k head is RMS-normed with them (eps) after the scales and before the rotation
 void rope_cache_write(torch::Tensor qkv, torch::Tensor positions, torch::Tensor slots, torch::Tensor cos,
                       torch::Tensor sin, torch::Tensor k_cache, torch::Tensor v_cache, int64_t H, int64_t KVH,
                       double k_scale, double v_scale, c10::optional<torch::Tensor> rs,
-                      c10::optional<torch::Tensor> cs) {
+                      c10::optional<torch::Tensor> cs, c10::optional<torch::Tensor> q_norm,
+                      c10::optional<torch::Tensor> k_norm, double eps) {
   check_bf16(qkv, "qkv");
   check_i32(positions, "positions");
   check_i32(slots, "slots");
@@ -1094,9 +1097,21 @@ void rope_cache_write(torch::Tensor qkv, torch::Tensor positions, torch::Tensor 
     rp = rs->data_ptr<float>();
     cp = cs->data_ptr<float>();
   }
+  TORCH_CHECK(q_norm.has_value() == k_norm.has_value(), "rope_cache_write: q_norm and k_norm go together");
+  const float* qw = nullptr;
+  const float* kw = nullptr;
+  if (q_norm.has_value()) {
+    for (const torch::Tensor* w : {&*q_norm, &*k_norm})
+      TORCH_CHECK(w->is_cuda() && w->scalar_type() == torch::kFloat32 && w->is_contiguous() && w->numel() == 128 &&
+                      reinterpret_cast<uintptr_t>(w->data_ptr()) % 16 == 0,
+                  "rope_cache_write: q_norm and k_norm must be fp32 [128], 16-byte aligned");
+    TORCH_CHECK(eps >= 0, "rope_cache_write: eps must not be negative");
+    qw = q_norm->data_ptr<float>();
+    kw = k_norm->data_ptr<float>();
+  }
   check(dsa_rope_cache_write(qkv.data_ptr(), positions.data_ptr<int>(), slots.data_ptr<int>(), cos.data_ptr<float>(),
                              sin.data_ptr<float>(), k_cache.data_ptr(), v_cache.data_ptr(), (int)T, (int)H, (int)KVH,
-                             fp8 ? 1 : 0, (float)k_scale, (float)v_scale, rp, cp, stream()),
+                             fp8 ? 1 : 0, (float)k_scale, (float)v_scale, rp, cp, qw, kw, (float)eps, stream()),
         "rope_cache_write");
 }
 
@@ -1550,7 +1565,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("paged_page_size", &dsa_paged_page_size);
   m.def("rope_cache_write", &rope_cache_write, py::arg("qkv"), py::arg("positions"), py::arg("slots"), py::arg("cos"),
         py::arg("sin"), py::arg("k_cache"), py::arg("v_cache"), py::arg("H"), py::arg("KVH"), py::arg("k_scale"),
-        py::arg("v_scale"), py::arg("rs") = py::none(), py::arg("cs") = py::none());
+        py::arg("v_scale"), py::arg("rs") = py::none(), py::arg("cs") = py::none(), py::arg("q_norm") = py::none(),
+        py::arg("k_norm") = py::none(), py::arg("eps") = 1e-6);
   m.def("paged_decode", &paged_decode);
   m.def("paged_verify", &paged_verify);
   m.def("paged_prefill", &paged_prefill, py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"),

@@ -39,6 +39,45 @@ __device__ __forceinline__ unsigned int to_fp8x4(const float* x, float s) {
   return __builtin_amdgcn_cvt_pk_fp8_f32(sat(x[2]), sat(x[3]), w, true);
 }
 
+// k (token-major row) or v (dim-major column) of one head chunk -> cache slot `slot` (>= 0): a / b are
+// the bf16 elements 8c..8c+7 and 64+8c..64+8c+7 of head `head` (>= H)
+template <bool FP8>
+__device__ __forceinline__ void cache_store(const us8 a, const us8 b, int head, int c, int slot, int H, int KVH,
+                                            void* __restrict__ k_cache, void* __restrict__ v_cache, float inv_ks,
+                                            float inv_vs) {
+  constexpr int half = HDIM / 2;
+  const int page = slot / PAGE, off = slot % PAGE;
+  if constexpr (FP8) {
+    if (head < H + KVH) {
+      unsigned char* dst = (unsigned char*)k_cache + (((size_t)page * KVH + (head - H)) * PAGE + off) * HDIM;
+      float x[8], y[8];
+      unpack8(a, x);
+      unpack8(b, y);
+      *reinterpret_cast<u2_t*>(dst + c * 8) = u2_t{to_fp8x4(x, inv_ks), to_fp8x4(x + 4, inv_ks)};
+      *reinterpret_cast<u2_t*>(dst + half + c * 8) = u2_t{to_fp8x4(y, inv_ks), to_fp8x4(y + 4, inv_ks)};
+    } else {
+      unsigned char* dst =
+          (unsigned char*)v_cache + ((size_t)page * KVH + (head - H - KVH)) * HDIM * PAGE + off;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        dst[(size_t)(c * 8 + k) * PAGE] = to_fp8(bf2f(a[k]) * inv_vs);
+        dst[(size_t)(half + c * 8 + k) * PAGE] = to_fp8(bf2f(b[k]) * inv_vs);
+      }
+    }
+  } else if (head < H + KVH) {
+    bf16_t* dst = (bf16_t*)k_cache + (((size_t)page * KVH + (head - H)) * PAGE + off) * HDIM;
+    *reinterpret_cast<us8*>(dst + c * 8) = a;
+    *reinterpret_cast<us8*>(dst + half + c * 8) = b;
+  } else {
+    bf16_t* dst = (bf16_t*)v_cache + ((size_t)page * KVH + (head - H - KVH)) * HDIM * PAGE + off;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      dst[(size_t)(c * 8 + k) * PAGE] = a[k];
+      dst[(size_t)(half + c * 8 + k) * PAGE] = b[k];
+    }
+  }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -116,36 +155,101 @@ __global__ __launch_bounds__(256) void rope_cache_write_kernel(bf16_t* __restric
     }
     const int slot = slots[t];
     if (head < H || slot < 0) continue;
-    const int page = slot / PAGE, off = slot % PAGE;
-    if constexpr (FP8) {
-      if (head < H + KVH) {
-        unsigned char* dst = (unsigned char*)k_cache + (((size_t)page * KVH + (head - H)) * PAGE + off) * HDIM;
-        float x[8], y[8];
-        unpack8(a, x);
-        unpack8(b, y);
-        *reinterpret_cast<u2_t*>(dst + c * 8) = u2_t{to_fp8x4(x, inv_ks), to_fp8x4(x + 4, inv_ks)};
-        *reinterpret_cast<u2_t*>(dst + half + c * 8) = u2_t{to_fp8x4(y, inv_ks), to_fp8x4(y + 4, inv_ks)};
-      } else {
-        unsigned char* dst =
-            (unsigned char*)v_cache + ((size_t)page * KVH + (head - H - KVH)) * HDIM * PAGE + off;
+    cache_store<FP8>(a, b, head, c, slot, H, KVH, k_cache, v_cache, inv_ks, inv_vs);
+  }
+}
+
+// Sum of v over the 8 consecutive lanes that hold one head, by an xor butterfly on the DPP path
+// (no LDS, no bpermute): quad_perm [1,0,3,2] and [2,3,0,1] are lane ^ 1 and lane ^ 2; after them the
+// four lanes of a quad agree, so row_half_mirror (lane -> 7 - lane of its 8) hands each quad the other
+// quad's sum like lane ^ 4 would.  Both sides of every step add the same two numbers, so all 8 lanes
+// end with the same bits.  The 8 lanes must be active together (they read only each other).
+template <int CTRL>
+static __device__ __forceinline__ float dpp_from(float x) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, false));
+}
+static __device__ __forceinline__ float head_sum8(float v) {
+  v += dpp_from<0xB1>(v);   // quad_perm [1,0,3,2]
+  v += dpp_from<0x4E>(v);   // quad_perm [2,3,0,1]
+  v += dpp_from<0x141>(v);  // row_half_mirror
+  return v;
+}
+
+// The q/k-norm form (Qwen3): every q and k head is RMS-normed over its 128 dims between the projection
+// and the rotation, n_j = x_j * rsqrt(mean(x^2) + eps) * w_j with w = q_w [128] for q heads and
+// k_w [128] for k heads (fp32, re-read per token and head: served from cache).  A head's 8 threads are
+// 8 consecutive lanes (total = T*NH*8, so they enter and leave the loop together): each squares and sums
+// its 16 values in fp32 and head_sum8 combines them.  Norm and rotation run in fp32 on un-rounded
+// values; the one rounding to bf16 is at the store.  SC: the scales come first, rounded to bf16 as in
+// the plain form.  v heads take no part (the branch diverges per 8 lanes) and are cached as there.
+template <bool FP8, bool SC>
+__global__ __launch_bounds__(256) void rope_cache_write_qknorm_kernel(
+    bf16_t* __restrict__ qkv, const int* __restrict__ positions, const int* __restrict__ slots,
+    const float* __restrict__ cosT, const float* __restrict__ sinT, void* __restrict__ k_cache,
+    void* __restrict__ v_cache, int T, int H, int KVH, float inv_ks, float inv_vs, const float* __restrict__ rs,
+    const float* __restrict__ cs, const float* __restrict__ q_w, const float* __restrict__ k_w, float eps) {
+  constexpr int half = HDIM / 2, cph = half / 8;
+  const int NH = H + 2 * KVH;
+  const size_t total = (size_t)T * NH * cph;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total;
+       i += (size_t)gridDim.x * blockDim.x) {
+    const int t = (int)(i / ((size_t)NH * cph));
+    const int rem = (int)(i % ((size_t)NH * cph));
+    const int head = rem / cph, c = rem % cph;
+    bf16_t* row = qkv + (size_t)t * NH * HDIM + (size_t)head * HDIM;
+    us8 a = *reinterpret_cast<const us8*>(row + c * 8);
+    us8 b = *reinterpret_cast<const us8*>(row + half + c * 8);
+    float x1[8], x2[8];
+    unpack8(a, x1);
+    unpack8(b, x2);
+    if constexpr (SC) {
+      const float r = rs[t];
+      const float* cc = cs + (size_t)head * HDIM + c * 8;
+      const f4 ca0 = *reinterpret_cast<const f4*>(cc), ca1 = *reinterpret_cast<const f4*>(cc + 4);
+      const f4 cb0 = *reinterpret_cast<const f4*>(cc + half), cb1 = *reinterpret_cast<const f4*>(cc + half + 4);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          dst[(size_t)(c * 8 + k) * PAGE] = to_fp8(bf2f(a[k]) * inv_vs);
-          dst[(size_t)(half + c * 8 + k) * PAGE] = to_fp8(bf2f(b[k]) * inv_vs);
-        }
+      for (int k = 0; k < 4; ++k) {
+        x1[k] = bf2f(f2bf(x1[k] * r * ca0[k]));
+        x1[4 + k] = bf2f(f2bf(x1[4 + k] * r * ca1[k]));
+        x2[k] = bf2f(f2bf(x2[k] * r * cb0[k]));
+        x2[4 + k] = bf2f(f2bf(x2[4 + k] * r * cb1[k]));
       }
-    } else if (head < H + KVH) {
-      bf16_t* dst = (bf16_t*)k_cache + (((size_t)page * KVH + (head - H)) * PAGE + off) * HDIM;
-      *reinterpret_cast<us8*>(dst + c * 8) = a;
-      *reinterpret_cast<us8*>(dst + half + c * 8) = b;
-    } else {
-      bf16_t* dst = (bf16_t*)v_cache + ((size_t)page * KVH + (head - H - KVH)) * HDIM * PAGE + off;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        dst[(size_t)(c * 8 + k) * PAGE] = a[k];
-        dst[(size_t)(half + c * 8 + k) * PAGE] = b[k];
+      if (head >= H + KVH) {  // v heads: the scaled values back in place
+        a = pack8(x1);
+        b = pack8(x2);
+        *reinterpret_cast<us8*>(row + c * 8) = a;
+        *reinterpret_cast<us8*>(row + half + c * 8) = b;
       }
     }
+    if (head < H + KVH) {  // q and k heads: norm, then rotate
+      float ss = 0.f;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) ss += x1[k] * x1[k] + x2[k] * x2[k];
+      const float inv = rsqrtf(head_sum8(ss) * (1.f / HDIM) + eps);
+      const float* wp = (head < H ? q_w : k_w) + c * 8;
+      const f4 wa0 = *reinterpret_cast<const f4*>(wp), wa1 = *reinterpret_cast<const f4*>(wp + 4);
+      const f4 wb0 = *reinterpret_cast<const f4*>(wp + half), wb1 = *reinterpret_cast<const f4*>(wp + half + 4);
+      const int pos = positions[t];
+      const f4* cp = reinterpret_cast<const f4*>(cosT + (size_t)pos * half + c * 8);
+      const f4* sp = reinterpret_cast<const f4*>(sinT + (size_t)pos * half + c * 8);
+      const f4 c0 = cp[0], c1 = cp[1], s0 = sp[0], s1 = sp[1];
+      float o1[8], o2[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const float n1 = x1[k] * inv * (k < 4 ? wa0[k & 3] : wa1[k & 3]);
+        const float n2 = x2[k] * inv * (k < 4 ? wb0[k & 3] : wb1[k & 3]);
+        const float co = k < 4 ? c0[k & 3] : c1[k & 3], si = k < 4 ? s0[k & 3] : s1[k & 3];
+        o1[k] = n1 * co - n2 * si;
+        o2[k] = n2 * co + n1 * si;
+      }
+      a = pack8(o1);
+      b = pack8(o2);
+      *reinterpret_cast<us8*>(row + c * 8) = a;
+      *reinterpret_cast<us8*>(row + half + c * 8) = b;
+    }
+    const int slot = slots[t];
+    if (head < H || slot < 0) continue;
+    cache_store<FP8>(a, b, head, c, slot, H, KVH, k_cache, v_cache, inv_ks, inv_vs);
   }
 }
 
@@ -488,12 +592,20 @@ extern "C" int dsa_paged_page_size() { return PAGE; }
 extern "C" hipError_t dsa_rope_cache_write(void* qkv, const int* positions, const int* slots,
                                            const float* cosT, const float* sinT, void* k_cache,
                                            void* v_cache, int T, int H, int KVH, int fp8, float k_scale,
-                                           float v_scale, const float* rs, const float* cs, hipStream_t st) {
+                                           float v_scale, const float* rs, const float* cs, const float* q_w,
+                                           const float* k_w, float eps, hipStream_t st) {
   if (T <= 0) return hipSuccess;
-  if ((rs == nullptr) != (cs == nullptr)) return hipErrorInvalidValue;
+  if ((rs == nullptr) != (cs == nullptr) || (q_w == nullptr) != (k_w == nullptr)) return hipErrorInvalidValue;
   const size_t work = (size_t)T * (H + 2 * KVH) * (HDIM / 16);
   size_t grid = (work + 255) / 256;
   if (grid > 65535 * 4) grid = 65535 * 4;
+  if (q_w) {  // the q/k-norm forms: {bf16, fp8 cache} x {plain, rs / cs}
+    auto* kern = fp8 ? (rs ? rope_cache_write_qknorm_kernel<true, true> : rope_cache_write_qknorm_kernel<true, false>)
+                     : (rs ? rope_cache_write_qknorm_kernel<false, true> : rope_cache_write_qknorm_kernel<false, false>);
+    kern<<<(unsigned)grid, 256, 0, st>>>((bf16_t*)qkv, positions, slots, cosT, sinT, k_cache, v_cache, T, H, KVH,
+                                         fp8 ? 1.f / k_scale : 1.f, fp8 ? 1.f / v_scale : 1.f, rs, cs, q_w, k_w, eps);
+    return hipGetLastError();
+  }
   if (rs && fp8)
     rope_cache_write_kernel<true, true><<<(unsigned)grid, 256, 0, st>>>(
         (bf16_t*)qkv, positions, slots, cosT, sinT, k_cache, v_cache, T, H, KVH, 1.f / k_scale, 1.f / v_scale, rs, cs);

@@ -41,27 +41,37 @@ def _is_fp8(cache: torch.Tensor) -> bool:
 # ----------------------------------------------------------------------------------------------
 def rope_cache_write(qkv: torch.Tensor, positions: torch.Tensor, slots: torch.Tensor, cos: torch.Tensor,
                      sin: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, n_heads: int,
-                     n_kv_heads: int, k_scale: float = 1.0, v_scale: float = 1.0, rs=None, cs=None) -> torch.Tensor:
+                     n_kv_heads: int, k_scale: float = 1.0, v_scale: float = 1.0, rs=None, cs=None, q_norm=None,
+                     k_norm=None, eps: float = 1e-6) -> torch.Tensor:
     """Rotate q and k of ``qkv`` [T, (H + 2*KVH) * 128] in place (token t at ``positions[t]``) and
     store k/v of every token with ``slots[t] >= 0`` in the cache.  Returns ``qkv``.
 
     ``rs`` [T] / ``cs`` [(H + 2*KVH) * 128]: ``qkv`` is the raw product of a tensor-wise-scaled fp8
-    GEMM; its row-wise scales are applied first, in place for every head."""
+    GEMM; its row-wise scales are applied first, in place for every head.
+
+    ``q_norm`` / ``k_norm`` (fp32 [128], together; Qwen3): every q head and every k head is RMS-normed
+    over its 128 dims, ``x * rsqrt(mean(x^2) + eps) * w``, after the scales and before the rotation,
+    in fp32 with one rounding at the end (same kernel, no extra pass over ``qkv``)."""
+    if (q_norm is None) != (k_norm is None):
+        raise ValueError("rope_cache_write: q_norm and k_norm go together")
     if _ext.use_hip(qkv):
         _ext.require().rope_cache_write(qkv, positions, slots, cos, sin, k_cache, v_cache, n_heads, n_kv_heads,
-                                        k_scale, v_scale, rs, cs)
+                                        k_scale, v_scale, rs, cs, q_norm, k_norm, eps)
         return qkv
     if rs is not None:
         qkv.copy_((qkv.float() * rs[:, None] * cs[None, :]).to(qkv.dtype))
     return rope_cache_write_ref(qkv, positions, slots, cos, sin, k_cache, v_cache, n_heads, n_kv_heads,
-                                k_scale, v_scale)
+                                k_scale, v_scale, q_norm, k_norm, eps)
 
 
 def rope_cache_write_ref(qkv, positions, slots, cos, sin, k_cache, v_cache, n_heads, n_kv_heads,
-                         k_scale: float = 1.0, v_scale: float = 1.0):
+                         k_scale: float = 1.0, v_scale: float = 1.0, q_norm=None, k_norm=None, eps: float = 1e-6):
     T = positions.numel()
     x = qkv.view(T, n_heads + 2 * n_kv_heads, HEAD_DIM)
     rot = x[:, : n_heads + n_kv_heads].float()
+    if q_norm is not None:  # per-head RMSNorm in front of the rotation, nothing rounded in between
+        w = torch.cat([q_norm.float().expand(n_heads, -1), k_norm.float().expand(n_kv_heads, -1)])
+        rot = rot * torch.rsqrt(rot.pow(2).mean(-1, keepdim=True) + eps) * w
     c = cos[positions.long()].unsqueeze(1)
     s = sin[positions.long()].unsqueeze(1)
     x1, x2 = rot[..., : HEAD_DIM // 2], rot[..., HEAD_DIM // 2 :]

@@ -133,12 +133,12 @@ def parse_lora_modules(items) -> dict:
 
 
 def write_random_adapter(path: str, cfg, rank: int, seed: int = 0, std: float = 0.02, targets=tuple(TARGETS),
-                         dtype=torch.bfloat16) -> str:
+                         dtype=torch.bfloat16, head_dim: int | None = None) -> str:
     """Write a PEFT-format adapter of ``rank`` with A, B ~ N(0, std) on ``targets`` for a model of
     config ``cfg`` (``LlamaConfig``) into ``path`` (benchmarks and tests: no trained adapter needed)."""
     from safetensors.torch import save_file
 
-    hd, d, f = cfg.head_dim, cfg.dim, cfg.ffn_dim
+    hd, d, f = head_dim or cfg.head_dim, cfg.dim, cfg.ffn_dim  # (head_dim: ModelSpec.head_dim, qwen3)
     shapes = {"q_proj": (cfg.n_heads * hd, d), "k_proj": (cfg.n_kv_heads * hd, d), "v_proj": (cfg.n_kv_heads * hd, d),
               "o_proj": (d, cfg.n_heads * hd), "gate_proj": (f, d), "up_proj": (f, d), "down_proj": (d, f)}
     g = torch.Generator().manual_seed(seed)

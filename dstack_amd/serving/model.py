@@ -203,8 +203,10 @@ class ModelSpec:
     bos_token_id: int | None = None
     eos_token_ids: tuple = ()
     path: str | None = None  # HF checkpoint directory (None: random init)
-    family: str = "llama"  # llama | mistral | qwen2 (same block; qwen2 adds q/k/v biases)
+    family: str = "llama"  # llama | mistral | qwen2 | qwen3 (same block; qwen2 adds q/k/v biases, qwen3 a q/k norm)
     qkv_bias: bool = False
+    qk_norm: bool = False  # qwen3: per-head RMSNorm of q and k between the projection and RoPE
+    head_dim: int | None = None  # where heads * head_dim is not hidden_size (qwen3); None: cfg.head_dim
     awq: AwqConfig | None = None  # the checkpoint's projections are AWQ 4-bit (config.json quantization_config)
     n_experts: int = 0  # mixtral: experts per layer in place of the dense MLP (0: dense)
     experts_per_tok: int = 0  # mixtral: experts the router picks per token
@@ -221,7 +223,9 @@ def load_spec(model: str) -> ModelSpec:
     """``model`` is a built-in config name (``llama-3-8b``, ``llama-3-70b``, …: random weights) or an
     HF checkpoint directory (``config.json`` + ``*.safetensors``) of the Llama block family: Llama
     2/3/3.x, Mistral (sliding-window models are served up to their window), Qwen2 / Qwen2.5
-    (q/k/v projection biases) and Mixtral (the Mistral block with ``num_local_experts`` experts behind a
+    (q/k/v projection biases), Qwen3 dense (no biases; a per-head RMSNorm of q and k in front of RoPE,
+    ``ModelSpec.qk_norm``; ``head_dim`` 128 from ``config.json`` with any ``hidden_size``,
+    ``ModelSpec.head_dim``) and Mixtral (the Mistral block with ``num_local_experts`` experts behind a
     router that picks ``num_experts_per_tok`` per token; ``mixtral-8x7b`` is built in).  A checkpoint whose ``config.json`` has a ``quantization_config`` must be
     an AutoAWQ 4-bit "GEMM" one (``ModelSpec.awq``); anything else in it is an error naming the field."""
     if model in CONFIGS:
@@ -242,7 +246,12 @@ def load_spec(model: str) -> ModelSpec:
     heads = hf["num_attention_heads"]
     dim = hf["hidden_size"]
     head_dim = hf.get("head_dim") or dim // heads
-    if head_dim != 128 or dim != heads * head_dim:
+    if family == "qwen3":  # the attention width heads * head_dim need not be hidden_size
+        if head_dim != 128:
+            raise ValueError(f"head_dim must be 128 (got {head_dim})")
+        if hf.get("attention_bias"):  # (false in every release; the loader has no place for the tensors)
+            raise ValueError("unsupported attention_bias=true in a qwen3 config.json (q/k/v/o biases)")
+    elif head_dim != 128 or dim != heads * head_dim:
         raise ValueError(f"head_dim must be 128 with hidden_size = heads * head_dim (got {head_dim})")
     # rope: ``rope_theta`` + ``rope_scaling`` (transformers 4.x) or ``rope_parameters`` (5.x)
     rp = hf.get("rope_parameters") or {}
@@ -279,11 +288,12 @@ def load_spec(model: str) -> ModelSpec:
         n_experts, per_tok = int(hf.get("num_local_experts", 8)), int(hf.get("num_experts_per_tok", 2))
         sops.moe_check(n_experts, per_tok)
     return ModelSpec(cfg, scaling, bool(hf.get("tie_word_embeddings", False)), hf.get("bos_token_id"), eos_ids,
-                     path=model, family=family, qkv_bias=family == "qwen2", awq=awq, n_experts=n_experts,
+                     path=model, family=family, qkv_bias=family == "qwen2", qk_norm=family == "qwen3",
+                     head_dim=head_dim if family == "qwen3" else None, awq=awq, n_experts=n_experts,
                      experts_per_tok=per_tok)
 
 
-SUPPORTED_FAMILIES = ("llama", "mistral", "qwen2", "mixtral")
+SUPPORTED_FAMILIES = ("llama", "mistral", "qwen2", "qwen3", "mixtral")
 
 
 def check_moe(spec: ModelSpec, quantization: str | None, tensor_parallel: bool, lora_modules=None):
@@ -336,7 +346,8 @@ class ServingLlama:
         self.cfg = cfg = spec.cfg
         self.device = torch.device(device)
         self.dtype = dtype or (torch.bfloat16 if self.device.type == "cuda" else torch.float32)
-        if cfg.head_dim != sops.HEAD_DIM:
+        head_dim = spec.head_dim or cfg.head_dim  # (the attention width H * D is not cfg.dim for qwen3)
+        if head_dim != sops.HEAD_DIM:
             raise ValueError("serving kernels need head_dim 128")
         self.max_model_len = max_model_len or cfg.max_seq_len
         self.tp_group = tp_group
@@ -346,7 +357,7 @@ class ServingLlama:
         if cfg.n_heads % tp or cfg.n_kv_heads % tp or cfg.ffn_dim % tp or cfg.vocab_size % tp:
             raise ValueError(f"tensor parallel {tp} must divide heads {cfg.n_heads}, kv heads {cfg.n_kv_heads}, "
                              f"ffn {cfg.ffn_dim} and vocab {cfg.vocab_size}")
-        self.H, self.KVH, self.D = cfg.n_heads // tp, cfg.n_kv_heads // tp, cfg.head_dim
+        self.H, self.KVH, self.D = cfg.n_heads // tp, cfg.n_kv_heads // tp, head_dim
         self.F, self.V = cfg.ffn_dim // tp, cfg.vocab_size // tp
         self.NH = self.H + 2 * self.KVH
         self.hip = self.device.type == "cuda" and not _ext.force_torch()
@@ -396,7 +407,7 @@ class ServingLlama:
 
     def allocate_weights(self):
         cfg = self.cfg
-        d, hd = cfg.dim, cfg.head_dim
+        d, hd = cfg.dim, self.D
         self.embed = self._empty(cfg.vocab_size, d)  # replicated (an index lookup)
         self.norm = self._empty(d)
         if self.spec.tie_embeddings:
@@ -421,6 +432,10 @@ class ServingLlama:
         if self.spec.qkv_bias:
             for L in self.layers:
                 L["bqkv"] = self._empty(self.NH * hd)
+        if self.spec.qk_norm:  # fp32 [128] each, as the cache-write kernel reads them; replicated across ranks
+            for L in self.layers:
+                L["q_norm"] = torch.ones(hd, dtype=torch.float32, device=self.device)
+                L["k_norm"] = torch.ones(hd, dtype=torch.float32, device=self.device)
 
     # ---- tensor-parallel sharding of full (unsharded) tensors ----
     def _shard(self, kind: str, t: torch.Tensor) -> torch.Tensor:
@@ -445,7 +460,7 @@ class ServingLlama:
         self.allocate_weights()
         cfg = self.cfg
         out_std = std / math.sqrt(2 * cfg.n_layers)
-        hd = cfg.head_dim
+        hd = self.D
 
         def draw(name, shape, sd):
             g = torch.Generator(device=self.device).manual_seed(zlib.crc32(f"{seed}:{name}".encode()))
@@ -547,6 +562,10 @@ class ServingLlama:
                             kind = key.split(".")[1][0]
                             lo = {"q": 0, "k": H * hd, "v": (H + KVH) * hd}[kind]
                             put(L["bqkv"][lo : lo + (H if kind == "q" else KVH) * hd], t, kind)
+                        elif key in ("self_attn.q_norm.weight", "self_attn.k_norm.weight") and self.spec.qk_norm:
+                            if tuple(t.shape) != (hd,):  # one weight per head dim, shared by all heads
+                                raise ValueError(f"{name}: expected [{hd}], got {list(t.shape)}")
+                            L[key.split(".")[1]].copy_(t.to(self.device, torch.float32))
                         elif self.E and key in ("block_sparse_moe.gate.weight", "mlp.gate.weight"):
                             put(L["router"], t)
                         elif self.E and len(parts) == 8 and parts[3:5] == ["block_sparse_moe", "experts"] \
@@ -589,6 +608,8 @@ class ServingLlama:
                 expected |= {f"model.layers.{i}.mlp.{k}" for k in ("gate.weight", "experts.gate_up_proj", "experts.down_proj")}
             if self.spec.qkv_bias:
                 expected |= {f"model.layers.{i}.self_attn.{p}_proj.bias" for p in "qkv"}
+            if self.spec.qk_norm:
+                expected |= {f"model.layers.{i}.self_attn.{p}_norm.weight" for p in "qk"}
         missing = expected - seen
         if missing:
             raise ValueError(f"checkpoint {path} is missing {len(missing)} tensors, e.g. {sorted(missing)[:3]}")
@@ -1134,6 +1155,12 @@ class ServingLlama:
     def _rows(h) -> int:
         return h.q.shape[0] if isinstance(h, Fp8Act) else h.shape[0]
 
+    def _qk_norm_args(self, L) -> dict:
+        """The q/k-norm keywords of ``sops.rope_cache_write`` for layer ``L`` (qwen3; none elsewhere)."""
+        if "q_norm" not in L:
+            return {}
+        return dict(q_norm=L["q_norm"], k_norm=L["k_norm"], eps=self.cfg.norm_eps)
+
     # ------------------------------------------------------------------------------------------
     # forward passes
     # ------------------------------------------------------------------------------------------
@@ -1202,6 +1229,7 @@ class ServingLlama:
             else:
                 x, h = self._add_rms(x, delta, L["attn_norm"], next_w=L["wqkv"])
             wq = L["wqkv"]
+            qkn = self._qk_norm_args(L)
             if isinstance(wq, Fp8Weight) and "bqkv" not in L:
                 # prefill-sized: the GEMM's row-wise scales are applied by the RoPE / cache-write kernel
                 r = self._mm_fp8(h, wq, defer="raw")
@@ -1212,13 +1240,13 @@ class ServingLlama:
             if isinstance(r, RawScaled):
                 qkv = r.raw
                 sops.rope_cache_write(qkv, positions, slots, self.cos, self.sin, self.k_cache[li], self.v_cache[li],
-                                      H, KVH, self.k_scale, self.v_scale, rs=r.rs, cs=r.cs)
+                                      H, KVH, self.k_scale, self.v_scale, rs=r.rs, cs=r.cs, **qkn)
             else:
                 qkv = r
                 if "bqkv" in L:
                     qkv = qkv + L["bqkv"]
                 sops.rope_cache_write(qkv, positions, slots, self.cos, self.sin, self.k_cache[li], self.v_cache[li],
-                                      H, KVH, self.k_scale, self.v_scale)
+                                      H, KVH, self.k_scale, self.v_scale, **qkn)
             # (a hit segment's padding rows are not written by the paged kernel: keep them finite)
             o = (torch.zeros if hit else torch.empty)(rows, H * self.D, dtype=x.dtype, device=x.device)
             if hit:
@@ -1287,7 +1315,7 @@ class ServingLlama:
             if "bqkv" in L:
                 qkv = qkv + L["bqkv"]
             sops.rope_cache_write(qkv, positions, slots, self.cos, self.sin, self.k_cache[li], self.v_cache[li], H, KVH,
-                                  self.k_scale, self.v_scale)
+                                  self.k_scale, self.v_scale, **self._qk_norm_args(L))
             o = attend(qkv, li)
             x, delta = self._mlp_and_attn_out(L, x, o, li, lora_idx)
         _, h = self._add_rms(x, delta, self.norm)
