@@ -31,7 +31,7 @@ ARCH = os.environ.get("DSTACK_AMD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # units compiled without the packed fp32 instructions (v_pk_{add,mul,fma}_f32): beside MFMAs they cost
 # issue cycles (csrc/w4.hip keeps its folds apart by hand); the older units keep the flags they were tuned with
-NO_PACKED_FP32 = {"moe"}
+NO_PACKED_FP32 = {"moe", "moe_w4"}
 
 
 def _torch_paths():

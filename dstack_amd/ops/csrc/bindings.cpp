@@ -124,6 +124,11 @@ bool dsa_moe_gemm_supported(int, int, int);
 int dsa_moe_gemm_split(int, int, int, int, int);
 hipError_t dsa_moe_gemm(const void*, long, int, int, const void*, const int*, const int*, float*, int, int, int, int, int,
                         int, hipStream_t);
+int dsa_moe_w4_gemm_form(int);
+bool dsa_moe_w4_gemm_supported(int, int, int, int);
+int dsa_moe_w4_gemm_split(int, int, int, int, int);
+hipError_t dsa_moe_w4_gemm(const void*, long, int, int, const void*, const void*, const void*, const int*, const int*,
+                           float*, int, int, int, int, int, int, int, hipStream_t);
 hipError_t dsa_moe_lists(const int*, const int*, int*, int*, int, int, int, hipStream_t);
 hipError_t dsa_moe_route(const void*, long, const void*, const int*, int*, float*, int*, int*, int, int, int, int,
                          hipStream_t);
@@ -900,6 +905,38 @@ void moe_gemm(torch::Tensor x, int64_t src_div, torch::Tensor W, torch::Tensor c
         "moe_gemm");
 }
 
+bool moe_w4_gemm_supported(int64_t R, int64_t N, int64_t K, int64_t g) {
+  return R <= INT_MAX && N <= INT_MAX && K <= INT_MAX && dsa_moe_w4_gemm_supported((int)R, (int)N, (int)K, (int)g);
+}
+
+// moe_gemm over W4 expert weights (csrc/moe_w4.hip): codes uint8 [E, N, K/2], zeros uint8 [E, N, K/g], scales
+// fp16 [E, N, K/g], every expert in ops.serving.w4_shuffle's stored form; the rest as moe_gemm
+void moe_w4_gemm(torch::Tensor x, int64_t src_div, torch::Tensor wc, torch::Tensor wz, torch::Tensor wsc, int64_t N,
+                 int64_t K, int64_t g, torch::Tensor counts, torch::Tensor lists, torch::Tensor part) {
+  TORCH_CHECK(x.dim() == 2 && wc.dim() == 3 && lists.dim() == 2 && part.dim() == 3,
+              "moe_w4_gemm: x [rows, K], codes [E, N, K/2], lists [E, R], part [S, R k, N]");
+  const int64_t E = wc.size(0), R = lists.size(1), S = part.size(0), P = part.size(1);
+  TORCH_CHECK(R >= 1 && P % R == 0, "moe_w4_gemm: part holds R k rows per K slice");
+  const int64_t k = P / R;
+  check_moe_dims(R, k, E, "moe_w4_gemm");
+  TORCH_CHECK(moe_w4_gemm_supported(R, N, K, g),
+              "moe_w4_gemm: 1 <= R <= 256, N % 256 == 0, K % 512 == 0, group size 32, 64 or 128");
+  TORCH_CHECK(S >= 1 && K % (512 * S) == 0, "moe_w4_gemm: K slices of whole 512-element groups");
+  TORCH_CHECK((src_div == 1 || src_div == k) && x.size(0) * src_div == P,
+              "moe_w4_gemm: x has a row per pair (src_div 1) or per token row (src_div k)");
+  check_moe_rows(x, K, "moe_w4_gemm x");
+  check_moe(wc, torch::kUInt8, {E, N, K / 2}, "moe_w4_gemm codes");
+  check_moe(wz, torch::kUInt8, {E, N, K / g}, "moe_w4_gemm zeros");
+  check_moe(wsc, torch::kFloat16, {E, N, K / g}, "moe_w4_gemm scales");
+  check_moe(counts, torch::kInt32, {E}, "moe_w4_gemm counts");
+  check_moe(lists, torch::kInt32, {E, R}, "moe_w4_gemm lists");
+  check_moe(part, torch::kFloat32, {S, P, N}, "moe_w4_gemm part");
+  check(dsa_moe_w4_gemm(x.data_ptr(), x.stride(0), (int)x.size(0), (int)src_div, wc.data_ptr(), wz.data_ptr(),
+                        wsc.data_ptr(), counts.data_ptr<int>(), lists.data_ptr<int>(), part.data_ptr<float>(), (int)R,
+                        (int)k, (int)E, (int)N, (int)K, (int)g, (int)S, stream()),
+        "moe_w4_gemm");
+}
+
 // a[p] = bf16(silu(g) u) from part fp32 [S, R k, 2F] for the pairs of live rows: a bf16 [R k, F]
 void moe_swiglu(torch::Tensor part, torch::Tensor live, torch::Tensor a) {
   TORCH_CHECK(part.dim() == 3 && live.dim() == 1 && part.size(1) % live.size(0) == 0 && part.size(2) % 8 == 0,
@@ -1546,6 +1583,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return dsa_moe_gemm_split((int)R, (int)k, (int)E, (int)N, (int)K);
         },
         "K slices the MoE MLP runs this shape with (0: unsupported)");
+  m.def("moe_w4_gemm", &moe_w4_gemm, pybind11::arg("x"), pybind11::arg("src_div"), pybind11::arg("codes"),
+        pybind11::arg("zeros"), pybind11::arg("scales"), pybind11::arg("N"), pybind11::arg("K"), pybind11::arg("g"),
+        pybind11::arg("counts"), pybind11::arg("lists"), pybind11::arg("part"));
+  m.def("moe_w4_gemm_supported", &moe_w4_gemm_supported);
+  m.def("moe_w4_gemm_form", [](int64_t R) { return dsa_moe_w4_gemm_form((int)R); },
+        "16-token blocks of the moe_w4_gemm form that runs R rows (1, 2, 4, 8 or 16)");
+  m.def("moe_w4_gemm_split",
+        [](int64_t R, int64_t k, int64_t E, int64_t N, int64_t K) {
+          return dsa_moe_w4_gemm_split((int)R, (int)k, (int)E, (int)N, (int)K);
+        },
+        "K slices the W4 MoE MLP runs this shape with (0: unsupported)");
   m.def("swiglu_quant_fp8_rows", &swiglu_quant_fp8_rows, py::arg("gu"), py::arg("rs") = py::none(),
         py::arg("cs") = py::none());
   m.def("scale_rows_cols_", &scale_rows_cols_);

@@ -49,9 +49,10 @@
 
 #include <type_traits>
 
-#include "stream_frag.h"
+#include "w4_frag.h"
 
 using namespace dsa;
+using namespace dsa::w4;  // w4_load_sz, w4_expand, w4_half, w4_convert, w4_fold
 using stream::f32x4;
 using stream::i32x4;
 
@@ -101,81 +102,14 @@ __device__ __forceinline__ void w4_load_w(__amdgpu_buffer_rsrc_t wrs, const unsi
   }
 }
 
-// a lane's scales (GS groups x 4 fp16 = 2 GS dwords) and zeros (GS groups x 4 bytes = GS dwords) of one step
-template <int NF, int TB, int GS>
-__device__ __forceinline__ void w4_load_sz(__amdgpu_buffer_rsrc_t srs, __amdgpu_buffer_rsrc_t zrs,
-                                           const unsigned (&soff)[NF], const unsigned (&zoff)[NF], int sso, int zso,
-                                           int (&sc)[NF][2 * GS], int (&zp)[NF][GS]) {
-#pragma unroll
-  for (int f = 0; f < NF; ++f) {
-    if constexpr (GS == 1) {
-      const auto a = __builtin_amdgcn_raw_buffer_load_b64(srs, (int)soff[f], sso, 0);
-      sc[f][0] = (int)a[0], sc[f][1] = (int)a[1];
-      zp[f][0] = (int)__builtin_amdgcn_raw_buffer_load_b32(zrs, (int)zoff[f], zso, 0);
-    } else if constexpr (GS == 2) {
-      const auto a = __builtin_amdgcn_raw_buffer_load_b128(srs, (int)soff[f], sso, 0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) sc[f][i] = (int)a[i];
-      const auto b = __builtin_amdgcn_raw_buffer_load_b64(zrs, (int)zoff[f], zso, 0);
-      zp[f][0] = (int)b[0], zp[f][1] = (int)b[1];
-    } else {
-      const auto a = __builtin_amdgcn_raw_buffer_load_b128(srs, (int)soff[f], sso, 0);
-      const auto a2 = __builtin_amdgcn_raw_buffer_load_b128(srs, (int)soff[f] + 16, sso, 0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) sc[f][i] = (int)a[i], sc[f][4 + i] = (int)a2[i];
-      const auto b = __builtin_amdgcn_raw_buffer_load_b128(zrs, (int)zoff[f], zso, 0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) zp[f][i] = (int)b[i];
-    }
-  }
-}
-
-// the 8 codes of one stored dword as the bf16 values 128 + q, in MFMA operand order.  mask = 0x000F000F
-// and bias = 0x43004300 come in registers (w4_gemm_kernel hides their values from the compiler): as
-// literals the compiler emits v_and_b32 + v_or_b32, the VOP3 v_and_or_b32 taking no literal
-__device__ __forceinline__ bf16x8 w4_expand(int d, unsigned mask, unsigned bias) {
-  const unsigned u = (unsigned)d;
-  const i32x4 v{(int)((u & mask) | bias), (int)(((u >> 4) & mask) | bias), (int)(((u >> 8) & mask) | bias),
-                (int)(((u >> 12) & mask) | bias)};
-  return __builtin_bit_cast(bf16x8, v);
-}
-
 // the 4 MFMA steps' B operands of one token block: token row r (st points at it), K chunks 4 kk + gq
 __device__ __forceinline__ void w4_read_x(const char* row, int r, int gq, bf16x8 (&xf)[4]) {
 #pragma unroll
   for (int kk = 0; kk < 4; ++kk) xf[kk] = *reinterpret_cast<const bf16x8*>(row + w4_chunk(r, 4 * kk + gq) * 16);
 }
 
-__device__ __forceinline__ float w4_half(unsigned bits) {
-  return (float)__builtin_bit_cast(_Float16, (unsigned short)bits);
-}
-
-// group G of a lane's raw scales and zeros of one step and fragment: s[e] fp32, zn[e] = 128 + z[e] (8
-// conversions: v_cvt_f32_f16 and v_cvt_f32_ubyte0..3 pick their half / byte themselves)
-template <int GS>
-__device__ __forceinline__ void w4_convert(const int (&sc)[2 * GS], const int (&zp)[GS], int G, float (&s)[4],
-                                           float (&zn)[4]) {
-  const unsigned s01 = (unsigned)sc[2 * G], s23 = (unsigned)sc[2 * G + 1], zb = (unsigned)zp[G];
-  s[0] = w4_half(s01 & 0xffffu), s[1] = w4_half(s01 >> 16);
-  s[2] = w4_half(s23 & 0xffffu), s[3] = w4_half(s23 >> 16);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) zn[e] = (float)((zb >> (8 * e)) & 0xffu);  // (the stored byte is 128 + z)
-}
-
 __device__ __forceinline__ f32x4 w4_mfma(const bf16x8& a, const bf16x8& b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-// acc += s (P - zn X) for the 4 accumulator registers of one fragment (zn = 128 + z), as 8 v_fma_f32
-__device__ __forceinline__ void w4_fold(f32x4& acc, const f32x4& P, float X, const float (&s)[4], const float (&zn)[4]) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float d = __builtin_fmaf(-zn[e], X, P[e]);
-    asm("" : "+v"(d));  // (an opaque value: the compiler cannot pair it with its neighbour into v_pk_fma_f32)
-    float a = __builtin_fmaf(s[e], d, acc[e]);
-    asm("" : "+v"(a));
-    acc[e] = a;
-  }
 }
 
 }  // namespace

@@ -1005,15 +1005,22 @@ class MoeWorkspace:
     graph holds their addresses): routing, the fp32 split-K partials of the larger of the two GEMMs
     at its largest row count, and the per-pair activations."""
 
-    def __init__(self, E: int, k: int, D: int, F: int, device):
+    def __init__(self, E: int, k: int, D: int, F: int, device, w4_group: int | None = None):
+        """``w4_group``: the experts are W4 (:func:`moe_w4_mlp`) with this group size -- the shapes are
+        checked against ``moe_w4_gemm`` and the per-row split table comes from its rule."""
         moe_check(E, k)
         C = _ext.require()
-        if not (C.moe_gemm_supported(MOE_MAX_ROWS, 2 * F, D) and C.moe_gemm_supported(MOE_MAX_ROWS, D, F)):
+        if w4_group is None:
+            ok, split = (lambda r, n, kk: C.moe_gemm_supported(r, n, kk)), C.moe_gemm_split
+        else:
+            ok, split = (lambda r, n, kk: C.moe_w4_gemm_supported(r, n, kk, w4_group)), C.moe_w4_gemm_split
+        if not (ok(MOE_MAX_ROWS, 2 * F, D) and ok(MOE_MAX_ROWS, D, F)):
             raise ValueError(f"mixture of experts: hidden size {D} and FFN size {F} must be multiples of 512 (the "
-                             "grouped decode GEMM's tiles)")
-        self.E, self.k, self.D, self.F = E, k, D, F
+                             "grouped decode GEMM's tiles)" + ("" if w4_group is None else
+                                                              f", the AWQ group size {w4_group} one of 32, 64, 128"))
+        self.E, self.k, self.D, self.F, self.w4_group = E, k, D, F, w4_group
         R = MOE_MAX_ROWS
-        self.split = {r: (C.moe_gemm_split(r, k, E, 2 * F, D), C.moe_gemm_split(r, k, E, D, F)) for r in range(1, R + 1)}
+        self.split = {r: (split(r, k, E, 2 * F, D), split(r, k, E, D, F)) for r in range(1, R + 1)}
         floats = max(max(s1 * r * k * 2 * F, s2 * r * k * D) for r, (s1, s2) in self.split.items())
         i32 = dict(dtype=torch.int32, device=device)
         self.topk_e, self.topk_w = torch.zeros(R * k, **i32), torch.zeros(R * k, dtype=torch.float32, device=device)
@@ -1048,6 +1055,12 @@ def moe_mlp_eager(h: torch.Tensor, router: torch.Tensor, wgu: torch.Tensor, wdow
     """The MoE MLP of any number of rows on library GEMMs (prefill): the pairs sorted by expert, one
     GEMM pair per non-empty expert, the weighted sum in fp32 and rounded once.  Reads the counts on the
     host once, so it cannot be captured."""
+    return _moe_mlp_eager(h, router, k, live, wdown.shape[1], wgu.__getitem__, wdown.__getitem__)
+
+
+def _moe_mlp_eager(h, router, k, live, D, gate_up, down):
+    """:func:`moe_mlp_eager` with the experts' weights behind two callables: ``gate_up(e)`` [2F, D] is
+    asked for first and multiplied before ``down(e)`` [D, F] is asked for (they may share a scratch)."""
     from dstack_amd.ops import reference as ref
 
     R, E = h.shape[0], router.shape[0]
@@ -1057,14 +1070,79 @@ def moe_mlp_eager(h: torch.Tensor, router: torch.Tensor, wgu: torch.Tensor, wdow
         flat = torch.where((live > 0).repeat_interleave(k), flat, torch.full_like(flat, E))
     order = torch.argsort(flat, stable=True)
     counts = torch.bincount(flat, minlength=E + 1).tolist()
-    y = torch.zeros(R, wdown.shape[1], dtype=torch.float32, device=h.device)
+    y = torch.zeros(R, D, dtype=torch.float32, device=h.device)
     wflat, start = topk_w.flatten(), 0
     for e in range(E):
         pairs, start = order[start : start + counts[e]], start + counts[e]
         if not counts[e]:
             continue
         rows = pairs // k
-        gu = h[rows] @ wgu[e].t()
+        gu = h[rows] @ gate_up(e).t()
         a = _ext.require().swiglu_fwd(gu) if _ext.use_hip(gu) else ref.swiglu(gu)
-        y.index_add_(0, rows, (a @ wdown[e].t()).float() * wflat[pairs][:, None])
+        y.index_add_(0, rows, (a @ down(e).t()).float() * wflat[pairs][:, None])
     return y.to(h.dtype)
+
+
+# ----------------------------------------------------------------------------------------------
+# The same MLP over W4 (AWQ) experts: csrc/moe_w4.hip
+# ----------------------------------------------------------------------------------------------
+# A stacked W4 expert weight [E, N, K] is the triple ``(codes uint8 [E, N, K/2], zeros uint8 [E, N, K/g],
+# scales fp16 [E, N, K/g])``, every expert in :func:`w4_shuffle`'s stored form (K % 128 == 0 here).
+def moe_w4_gemm_split(R: int, k: int, E: int, N: int, K: int) -> int:
+    """K slices the W4 grouped GEMM runs a shape with, from the shape alone (0: unsupported on the kernel)."""
+    return int(_ext.require().moe_w4_gemm_split(R, k, E, N, K))
+
+
+def moe_w4_dequant_ref(W, g: int) -> torch.Tensor:
+    """fp32 [E, N, K] values ``(q - z) * s`` of a stacked stored W4 weight (exact)."""
+    from dstack_amd.ops import reference as ref
+
+    return torch.stack([ref.dequant_w4(*w4_unshuffle(c, z, s, g), g) for c, z, s in zip(*W)])
+
+
+def moe_w4_gemm(x: torch.Tensor, src_div: int, W, g: int, counts: torch.Tensor, lists: torch.Tensor, split: int,
+                part: torch.Tensor | None = None) -> torch.Tensor:
+    """:func:`moe_gemm` with ``W`` a stacked W4 expert weight of group size ``g``: ``part[s, p] =
+    x[p // src_div] @ ((q - z) * s)[expert(p)]^T`` over K slice ``s``, fp32 [split, R k, N].  N % 256 == 0,
+    K % (512 split) == 0.  Without the kernels: the experts dequantized to fp32, then :func:`moe_gemm_ref`."""
+    codes, zeros, scales = W
+    if not _ext.use_hip(x):
+        return moe_gemm_ref(x, src_div, moe_w4_dequant_ref(W, g), counts, lists, split)
+    N, K = codes.shape[1], 2 * codes.shape[2]
+    if part is None:
+        part = torch.empty(split, x.shape[0] * src_div, N, dtype=torch.float32, device=x.device)
+    _ext.require().moe_w4_gemm(x, src_div, codes, zeros, scales, N, K, g, counts, lists, part)
+    return part
+
+
+def moe_w4_mlp(h: torch.Tensor, router: torch.Tensor, wgu, wdown, g: int, k: int, live: torch.Tensor,
+               ws: MoeWorkspace) -> torch.Tensor:
+    """:func:`moe_mlp` over W4 experts (``wgu`` [E, 2F, D], ``wdown`` [E, D, F], stacked stored weights of
+    group size ``g``): route, W4 gate/up GEMM, reduce + SwiGLU, W4 down GEMM, reduce + weighted sum.
+    Capturable.  ``ws``: a :class:`MoeWorkspace` made with ``w4_group=g``."""
+    assert ws.w4_group == g, (ws.w4_group, g)
+    R, E, D, F = h.shape[0], router.shape[0], ws.D, ws.F
+    if h.stride(-1) != 1 or h.stride(0) % 8 or h.data_ptr() % 16:
+        h = h.contiguous()
+    s1, s2 = ws.split[R]
+    P = R * k
+    topk_e, topk_w, counts, lists = moe_route(
+        h, router, live, k, out=(ws.topk_e[:P].view(R, k), ws.topk_w[:P].view(R, k), ws.counts, ws.lists[: E * R].view(E, R)))
+    part = moe_w4_gemm(h, k, wgu, g, counts, lists, s1, part=ws.part[: s1 * P * 2 * F].view(s1, P, 2 * F))
+    a = moe_swiglu(part, live, out=ws.a[:P])
+    part = moe_w4_gemm(a, 1, wdown, g, counts, lists, s2, part=ws.part[: s2 * P * D].view(s2, P, D))
+    return moe_combine(part, topk_w, live)
+
+
+def moe_w4_mlp_eager(h: torch.Tensor, router: torch.Tensor, wgu, wdown, g: int, k: int, live: torch.Tensor | None,
+                     scratch: torch.Tensor) -> torch.Tensor:
+    """:func:`moe_mlp_eager` over W4 experts (prefill): per non-empty expert its gate/up slice, then its
+    down slice, is dequantized exactly (``w4_dequant``: bf16((q - z) s)) into ``scratch`` (bf16, at least
+    2F D elements) and multiplied by the library GEMM.  No bf16 copy outlives its GEMM."""
+    C = _ext.require()
+
+    def deq(W, e):
+        N, K = W[0].shape[1], 2 * W[0].shape[2]
+        return C.w4_dequant(W[0][e], W[1][e], W[2][e], N, K, g, scratch[: N * K].view(N, K))
+
+    return _moe_mlp_eager(h, router, k, live, wdown[0].shape[1], lambda e: deq(wgu, e), lambda e: deq(wdown, e))

@@ -106,6 +106,50 @@ class Awq4Weight:
         return sops.w4_unshuffle(self.codes, self.zeros, self.scales, self.g, self.K)
 
 
+class Awq4Experts:
+    """The W4A16 weights [E, N, K] of a layer's experts (an AWQ Mixtral checkpoint): every expert in
+    :class:`Awq4Weight`'s stored form, stacked -- ``codes`` uint8 [E, N, K/2], ``zeros`` uint8
+    [E, N, K/g], ``scales`` fp16 [E, N, K/g] (K % 128 == 0).  The one copy: the grouped decode GEMM
+    (``ops/csrc/moe_w4.hip``) streams it, prefill dequantizes an expert at a time into a scratch."""
+
+    __slots__ = ("codes", "zeros", "scales", "E", "N", "K", "g")
+
+    def __init__(self, E: int, N: int, K: int, g: int, device):
+        if N % 16 or K % 128 or K % g:
+            raise ValueError(f"quantization=\"awq\": an expert projection [{N}, {K}] needs N % 16 == 0, K % 128 == 0 "
+                             f"and K % {g} == 0")
+        self.E, self.N, self.K, self.g = int(E), int(N), int(K), int(g)
+        self.codes = torch.zeros(E, N, K // 2, dtype=torch.uint8, device=device)
+        self.zeros = torch.zeros(E, N, K // g, dtype=torch.uint8, device=device)
+        self.scales = torch.zeros(E, N, K // g, dtype=torch.float16, device=device)
+
+    @property
+    def shape(self):
+        return torch.Size((self.E, self.N, self.K))
+
+    @property
+    def stored(self):
+        return self.codes, self.zeros, self.scales
+
+    def put(self, e: int, codes: torch.Tensor, zeros: torch.Tensor, scales: torch.Tensor):
+        """Expert ``e`` from its canonical form (``ops.reference.unpack_awq`` / ``quant_w4``)."""
+        if tuple(codes.shape) != (self.N, self.K // 2):
+            raise ValueError(f"expert {e}: canonical codes {list(codes.shape)} for a [{self.N}, {self.K}] projection")
+        for dst, src in zip(self.stored, sops.w4_shuffle(codes, zeros, scales, self.g)):
+            dst[e].copy_(src)
+
+    def nbytes(self) -> int:
+        return self.codes.numel() + self.zeros.numel() + 2 * self.scales.numel()
+
+    def canonical(self, e: int):
+        """(codes [N, K/2], zeros [N, K/g], scales [N, K/g]) of expert ``e`` in the canonical order."""
+        return sops.w4_unshuffle(self.codes[e], self.zeros[e], self.scales[e], self.g, self.K)
+
+    def dequantized(self) -> torch.Tensor:
+        """fp32 [E, N, K] values (q - z) * s (exact)."""
+        return sops.moe_w4_dequant_ref(self.stored, self.g)
+
+
 @dataclass
 class AwqConfig:
     """``quantization_config`` of an AutoAWQ checkpoint, as far as it is supported: 4 bits, "GEMM"
@@ -114,7 +158,7 @@ class AwqConfig:
     group_size: int = 128
 
 
-def _awq_config(qc: dict) -> AwqConfig:
+def _awq_config(qc: dict, family: str = "llama") -> AwqConfig:
     """Check an HF ``quantization_config``; every unsupported value is an error that names its field."""
     method = str(qc.get("quant_method", "")).lower()
     if method != "awq":
@@ -133,9 +177,11 @@ def _awq_config(qc: dict) -> AwqConfig:
     g = qc.get("group_size", qc.get("q_group_size", 128))
     if g not in ref.W4_GROUPS:
         raise ValueError(f"unsupported AWQ quantization_config: group_size = {g!r} (one of {ref.W4_GROUPS})")
-    if qc.get("modules_to_not_convert"):
-        raise ValueError(f"unsupported AWQ quantization_config: modules_to_not_convert = "
-                         f"{qc['modules_to_not_convert']!r} (every projection must be quantized)")
+    skip = qc.get("modules_to_not_convert")
+    if skip and not (family == "mixtral" and list(skip) == ["gate"]):  # (AutoAWQ leaves Mixtral's router in fp16)
+        raise ValueError(f"unsupported AWQ quantization_config: modules_to_not_convert = {skip!r} (every projection "
+                         "must be quantized" + ("; only the router, [\"gate\"], may stay out)" if family == "mixtral"
+                                                else ")"))
     return AwqConfig(group_size=int(g))
 
 
@@ -282,7 +328,7 @@ def load_spec(model: str) -> ModelSpec:
         raise ValueError(f"unsupported rope_scaling {rs}")
     eos = hf.get("eos_token_id")
     eos_ids = tuple(eos) if isinstance(eos, list) else ((eos,) if eos is not None else ())
-    awq = _awq_config(hf["quantization_config"]) if hf.get("quantization_config") else None
+    awq = _awq_config(hf["quantization_config"], family) if hf.get("quantization_config") else None
     n_experts = per_tok = 0
     if family == "mixtral":  # the Mistral block with the MLP replaced by experts behind a linear router
         n_experts, per_tok = int(hf.get("num_local_experts", 8)), int(hf.get("num_experts_per_tok", 2))
@@ -301,9 +347,12 @@ def check_moe(spec: ModelSpec, quantization: str | None, tensor_parallel: bool, 
     if not spec.n_experts:
         return
     sops.moe_check(spec.n_experts, spec.experts_per_tok)
-    if quantization is not None or spec.awq is not None:
-        raise ValueError(f"quantization={quantization or 'awq'!r} (--quantization) is not supported on a "
-                         "mixture-of-experts model: its experts are served in bf16")
+    if quantization not in (None, "awq"):
+        raise ValueError(f"quantization={quantization!r} (--quantization) is not supported on a mixture-of-experts "
+                         "model: its experts are served in bf16 or, from an AWQ checkpoint, in 4 bits")
+    if quantization == "awq" and spec.path and spec.awq is None:
+        raise ValueError(f"quantization=\"awq\" (--quantization) needs an AWQ checkpoint, and {spec.path} has no "
+                         "quantization_config in its config.json: there is no AWQ calibration here")
     if tensor_parallel:
         raise ValueError("tensor parallel (tp_group) is not supported on a mixture-of-experts model: a replica is one GPU")
     if lora_modules:
@@ -366,7 +415,10 @@ class ServingLlama:
         # mixture of experts: E experts per layer, k per token; on the GPU up to 256 rows run on the
         # kernels of csrc/moe.hip from one workspace (its constructor refuses shapes they do not cover)
         self.E, self.topk = spec.n_experts, spec.experts_per_tok
-        self.moe_ws = sops.MoeWorkspace(self.E, self.topk, cfg.dim, cfg.ffn_dim, self.device) if self.E and self.hip else None
+        # (AWQ experts: the W4 grouped GEMM of csrc/moe_w4.hip, at the checkpoint's group size; 128 built in)
+        self.moe_w4_group = (spec.awq.group_size if spec.awq else 128) if self.E and quantization == "awq" else None
+        self.moe_ws = sops.MoeWorkspace(self.E, self.topk, cfg.dim, cfg.ffn_dim, self.device,
+                                        w4_group=self.moe_w4_group) if self.E and self.hip else None
         self._moe_live = None  # int32 [rows] of the running step: > 0 where the row holds a token
         # DSTACK_AMD_GEMV=0: small decode batches on hipBLASLt too (A/B switch)
         self.gemv = os.environ.get("DSTACK_AMD_GEMV", "1") != "0"
@@ -416,6 +468,10 @@ class ServingLlama:
             self.lm_head = self._empty(self.V, d)
         if self.spec.awq is not None:  # the projections arrive 4-bit (load_hf): no bf16 copy is ever made
             self.layers = [dict(attn_norm=self._empty(d), ffn_norm=self._empty(d)) for _ in range(cfg.n_layers)]
+            for L in self.layers if self.E else ():  # the experts' stored form is filled expert by expert
+                g = self.spec.awq.group_size
+                L.update(router=self._empty(self.E, d), wgu=Awq4Experts(self.E, 2 * self.F, d, g, self.device),
+                         wdown=Awq4Experts(self.E, d, self.F, g, self.device))
         elif self.E:  # experts in place of the dense MLP: the one copy both the kernels and the eager path read
             self.layers = [
                 dict(attn_norm=self._empty(d), wqkv=self._empty(self.NH * hd, d), wo=self._empty(d, self.H * hd),
@@ -510,6 +566,10 @@ class ServingLlama:
         # AWQ checkpoint: a layer's 7 x (qweight, qzeros, scales) are collected on the host and turned
         # into its four stored weights as soon as the last one has arrived (``_put_awq_layer``)
         awq_pending: dict[int, dict] = {}
+        # (a mixture-of-experts model: the attention projections only; an expert's triplets are turned
+        # into its slice of the layer's stored experts as soon as they are complete, ``_put_awq_expert``)
+        awq_proj = {p: k for p, k in self.AWQ_PROJ.items() if not (self.E and p.startswith("mlp."))}
+        expert_pending: dict[int, dict] = {}
 
         def put(dst, src, kind=None):
             if kind is not None:
@@ -533,7 +593,9 @@ class ServingLlama:
                         L = self.layers[int(parts[2])]
                         key = ".".join(parts[3:])
                         proj, _, kind = key.rpartition(".")
-                        if proj in self.AWQ_PROJ and (kind in self.AWQ_KINDS or (kind == "weight" and awq)):
+                        expert = self.E and len(parts) == 8 and parts[3:5] == ["block_sparse_moe", "experts"] \
+                            and parts[5].isdigit() and int(parts[5]) < self.E and parts[6] in ("w1", "w2", "w3")
+                        if (proj in awq_proj or expert) and (kind in self.AWQ_KINDS or (kind == "weight" and awq)):
                             if awq is None:
                                 raise ValueError(f"unexpected tensor {name}: an AWQ tensor in a checkpoint whose "
                                                  "config.json has no quantization_config")
@@ -541,9 +603,16 @@ class ServingLlama:
                                 raise ValueError(f"unexpected tensor {name}: config.json says the checkpoint is AWQ, so "
                                                  f"this projection must come as {', '.join(self.AWQ_KINDS)}")
                             li = int(parts[2])
+                            if expert:  # AutoAWQ's Mixtral names: per expert w1 (gate), w3 (up), w2 (down)
+                                got = expert_pending.setdefault(li, {})
+                                got[(int(parts[5]), parts[6], kind)] = self._check_awq_tensor(name, parts[6], kind, t)
+                                self._put_awq_expert(L, got, int(parts[5]))
+                                if not got:
+                                    del expert_pending[li]
+                                continue
                             got = awq_pending.setdefault(li, {})
                             got[(proj, kind)] = self._check_awq_tensor(name, proj, kind, t)
-                            if len(got) == len(self.AWQ_PROJ) * len(self.AWQ_KINDS):
+                            if len(got) == len(awq_proj) * len(self.AWQ_KINDS):
                                 self._put_awq_layer(L, awq_pending.pop(li))
                         elif key == "input_layernorm.weight":
                             put(L["attn_norm"], t)
@@ -600,10 +669,11 @@ class ServingLlama:
             expected |= {f"model.layers.{i}.{k}.weight" for k in ("input_layernorm", "post_attention_layernorm")}
             expected |= {f"model.layers.{i}.{k}.{kind}" for k in self.AWQ_PROJ if not (self.E and k.startswith("mlp."))
                          for kind in (self.AWQ_KINDS if awq else ("weight",))}
-            if self.E and any(".block_sparse_moe." in n for n in seen):  # the Hub's per-expert tensors
+            if self.E and (awq or any(".block_sparse_moe." in n for n in seen)):  # the Hub's per-expert tensors
                 pre = f"model.layers.{i}.block_sparse_moe"
-                expected |= {f"{pre}.gate.weight"} | {f"{pre}.experts.{e}.{w}.weight" for e in range(self.E)
-                                                      for w in ("w1", "w2", "w3")}
+                expected |= {f"{pre}.gate.weight"} | {f"{pre}.experts.{e}.{w}.{kind}" for e in range(self.E)
+                                                      for w in ("w1", "w2", "w3")
+                                                      for kind in (self.AWQ_KINDS if awq else ("weight",))}
             elif self.E:  # the fused tensors
                 expected |= {f"model.layers.{i}.mlp.{k}" for k in ("gate.weight", "experts.gate_up_proj", "experts.down_proj")}
             if self.spec.qkv_bias:
@@ -627,9 +697,12 @@ class ServingLlama:
         qzeros int32 [K/g, N/8], scales fp16 [K/g, N])."""
         d, hd, g = self.cfg.dim, self.D, self.spec.awq.group_size
         N, K = {"q": (self.H * hd, d), "k": (self.KVH * hd, d), "v": (self.KVH * hd, d), "wo": (d, self.H * hd),
-                "gate": (self.F, d), "up": (self.F, d), "wdown": (d, self.F)}[self.AWQ_PROJ[proj]]
+                "gate": (self.F, d), "up": (self.F, d), "wdown": (d, self.F),
+                "w1": (self.F, d), "w3": (self.F, d), "w2": (d, self.F)}[self.AWQ_PROJ.get(proj, proj)]
         if K % g or N % 8:
             raise ValueError(f"{name}: a [{N}, {K}] projection has no whole groups of {g} / dwords of 8 columns")
+        if proj in ("w1", "w2", "w3") and N % 16:  # (an expert's stored form: 16-row blocks)
+            raise ValueError(f"{name}: an expert projection of {N} output rows is no multiple of 16")
         shape, dtype = {"qweight": ((K, N // 8), torch.int32), "qzeros": ((K // g, N // 8), torch.int32),
                         "scales": ((K // g, N), torch.float16)}[kind]
         if tuple(t.shape) != shape or t.dtype != dtype:
@@ -656,12 +729,25 @@ class ServingLlama:
 
         L["wqkv"] = fused("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj")
         L["wo"] = fused("self_attn.o_proj")
-        L["wgu"] = fused("mlp.gate_proj", "mlp.up_proj")
-        L["wdown"] = fused("mlp.down_proj")
+        if not self.E:  # (the experts of a mixture-of-experts layer: _put_awq_expert)
+            L["wgu"] = fused("mlp.gate_proj", "mlp.up_proj")
+            L["wdown"] = fused("mlp.down_proj")
+
+    def _put_awq_expert(self, L: dict, got: dict, e: int):
+        """Expert ``e``'s AWQ tensors collected so far (``got``: (expert, w1 | w2 | w3, kind) -> tensor):
+        once w1 (gate) and w3 (up) are both in, they are unpacked, concatenated along N with the gate
+        rows first, shuffled and copied into slice ``e`` of the layer's stored ``wgu``; w2 the same way
+        into ``wdown``.  What was used leaves ``got``."""
+        for dst, ws in (("wgu", ("w1", "w3")), ("wdown", ("w2",))):
+            keys = [(e, w, kind) for w in ws for kind in self.AWQ_KINDS]
+            if all(key in got for key in keys):
+                parts = [ref.unpack_awq(*(got.pop((e, w, kind)) for kind in self.AWQ_KINDS)) for w in ws]
+                L[dst].put(e, *(torch.cat([p[i] for p in parts]) for i in range(3)))
 
     def _alloc_w4_scratch(self):
-        """The bf16 scratch the prefill-sized W4 GEMMs dequantize into (the largest projection; a
-        workspace, not counted as weight bytes)."""
+        """The bf16 scratch the prefill-sized W4 GEMMs dequantize into (the largest projection -- of a
+        mixture-of-experts layer one expert's gate/up, 2F D elements; a workspace, not counted as
+        weight bytes)."""
         big = max(L[k].N * L[k].K for L in self.layers for k in self.FP8_KEYS)
         self._w4_scratch = torch.empty(big, dtype=torch.bfloat16, device=self.device) if self.hip else None
 
@@ -674,7 +760,14 @@ class ServingLlama:
         for L in self.layers:
             for k in self.FP8_KEYS:
                 w = L[k]
-                if isinstance(w, Awq4Weight):
+                if isinstance(w, (Awq4Weight, Awq4Experts)):
+                    continue
+                if w.dim() == 3:  # a mixture-of-experts layer's [E, N, K]: expert by expert
+                    q = Awq4Experts(*w.shape, g, self.device)
+                    for e in range(w.shape[0]):
+                        q.put(e, *ref.quant_w4(w[e], g))
+                    L[k] = q
+                    del w
                     continue
                 N, K = w.shape
                 if K % g:
@@ -786,7 +879,8 @@ class ServingLlama:
         n = sum(t.numel() * t.element_size() for t in ts)
         for L in self.layers:
             for t in L.values():
-                n += t.nbytes() if isinstance(t, (Fp8Weight, Mxfp4Weight, Awq4Weight)) else t.numel() * t.element_size()
+                n += t.nbytes() if isinstance(t, (Fp8Weight, Mxfp4Weight, Awq4Weight, Awq4Experts)) \
+                    else t.numel() * t.element_size()
         for L in self.lora:
             n += sum(t.numel() * t.element_size() for ab in L.values() for t in ab)
         return n
@@ -1144,7 +1238,22 @@ class ServingLlama:
         prefill) on the kernels of ``csrc/moe.hip`` -- no host read, so the step can be captured; more
         rows (prefill) on one library GEMM pair per non-empty expert (``sops.moe_mlp_eager``), which
         reads the routing counts on the host once per layer.  CPU: ``ref.moe_mlp`` for every row
-        count.  All three read the same ``wgu`` [E, 2F, D] and ``wdown`` [E, D, F]."""
+        count.  All three read the same ``wgu`` [E, 2F, D] and ``wdown`` [E, D, F].
+
+        AWQ experts (``Awq4Experts``): up to 256 rows on the W4 grouped GEMM of ``csrc/moe_w4.hip``
+        between the same router, SwiGLU and combine kernels (``sops.moe_w4_mlp``); more rows dequantize
+        one expert at a time into the W4 scratch for the library GEMM pair (``sops.moe_w4_mlp_eager``);
+        CPU: ``ref.moe_mlp`` on the experts dequantized to fp32."""
+        if isinstance(L["wgu"], Awq4Experts):
+            wgu, wdown = L["wgu"], L["wdown"]
+            if not self.hip:
+                return ref.moe_mlp(h, L["router"], wgu.dequantized().to(h.dtype), wdown.dequantized().to(h.dtype),
+                                   self.topk, self._moe_live)
+            if h.shape[0] <= sops.MOE_MAX_ROWS:
+                return sops.moe_w4_mlp(h, L["router"], wgu.stored, wdown.stored, wgu.g, self.topk, self._moe_live,
+                                       self.moe_ws)
+            return sops.moe_w4_mlp_eager(h, L["router"], wgu.stored, wdown.stored, wgu.g, self.topk, self._moe_live,
+                                         self._w4_scratch)
         if not self.hip:
             return ref.moe_mlp(h, L["router"], L["wgu"], L["wdown"], self.topk, self._moe_live)
         if h.shape[0] <= sops.MOE_MAX_ROWS:

@@ -9,7 +9,11 @@ Every call takes the next of several inputs, so consecutive calls choose other e
 chosen experts (at least 0.7 GB) exceed the 256 MB last-level cache.  The two paths alternate, REPS
 times after a warm-up; the spread is the min..max of a path's repetitions.
 
-    python tools/bench_moe.py [--out FILE]         # ROWS=1,16,64,256 REPS=5 ITERS=20
+``--w4``: the same shapes and rows with the experts as W4 (``quant_w4`` at g = 128, csrc/moe_w4.hip):
+``moe_w4_gemm`` beside the bf16 ``moe_gemm`` on the same routing, for the gate/up and the down GEMM, and
+the whole MLP of both, alternating under the same protocol.
+
+    python tools/bench_moe.py [--w4] [--out FILE]  # ROWS=1,16,64,256 REPS=5 ITERS=20
 """
 import argparse
 import os
@@ -34,9 +38,57 @@ def timed(fn, iters):
     return s.elapsed_time(e) / iters * 1e3  # us
 
 
+def w4_table(dev, draw, router, wgu, wdown, ws, rows, reps, iters, g=128):
+    from dstack_amd.ops import reference as ref
+
+    def quant(w):  # stacked stored form, expert by expert
+        return tuple(torch.stack(t) for t in zip(*(sops.w4_shuffle(*ref.quant_w4(w[e], g), g) for e in range(E))))
+
+    qgu, qdown = quant(wgu), quant(wdown)
+    ws4 = sops.MoeWorkspace(E, TOPK, D, F, dev, w4_group=g)
+    lines = [f"# {torch.cuda.get_device_name(0)}; Mixtral-8x7B MoE MLP (hidden {D}, FFN {F}, {E} experts, top-{TOPK}), W4 "
+             f"experts (g = {g}) beside bf16; us per call, median of {reps} x {iters} calls (min..max)",
+             "# rows form | split bf16(gu,down) w4(gu,down) | gate/up: bf16 us, w4 us, bf16/w4 | down: bf16 us, w4 us, "
+             "bf16/w4 | MLP: bf16 us, w4 us, bf16/w4"]
+    for R in rows:
+        hs = [draw(R, D, sd=1.0) for _ in range(8)]
+        acts = [draw(R * TOPK, F, sd=1.0) for _ in range(8)]
+        live = torch.ones(R, dtype=torch.int32, device=dev)
+        routed = [tuple(t.clone() for t in sops.moe_route(h, router, live, TOPK)) for h in hs]
+        (b1, b2), (s1, s2) = ws.split[R], ws4.split[R]
+        P = R * TOPK
+
+        def part(w, s, n):
+            return w.part[: s * P * n].view(s, P, n)
+
+        paths = {
+            "gu": lambda i: sops.moe_gemm(hs[i % 8], TOPK, wgu, *routed[i % 8][2:], b1, part=part(ws, b1, 2 * F)),
+            "gu4": lambda i: sops.moe_w4_gemm(hs[i % 8], TOPK, qgu, g, *routed[i % 8][2:], s1, part=part(ws4, s1, 2 * F)),
+            "dn": lambda i: sops.moe_gemm(acts[i % 8], 1, wdown, *routed[i % 8][2:], b2, part=part(ws, b2, D)),
+            "dn4": lambda i: sops.moe_w4_gemm(acts[i % 8], 1, qdown, g, *routed[i % 8][2:], s2, part=part(ws4, s2, D)),
+            "mlp": lambda i: sops.moe_mlp(hs[i % 8], router, wgu, wdown, TOPK, live, ws),
+            "mlp4": lambda i: sops.moe_w4_mlp(hs[i % 8], router, qgu, qdown, g, TOPK, live, ws4),
+        }
+        for fn in paths.values():
+            timed(fn, 8)
+        t = {name: [] for name in paths}
+        for _ in range(reps):
+            for name, fn in paths.items():
+                t[name].append(timed(fn, iters))
+        med = {name: statistics.median(v) for name, v in t.items()}
+        cell = {name: f"{med[name]:8.1f} ({min(v):.0f}..{max(v):.0f})" for name, v in t.items()}
+        lines.append(f"{R:6d} {sops._ext.require().moe_w4_gemm_form(R):4d} | {b1},{b2} {s1},{s2} | "
+                     + " | ".join(f"{cell[a]} {cell[a + '4']} {med[a] / med[a + '4']:.2f}x" for a in ("gu", "dn", "mlp")))
+        print(lines[-1], flush=True)
+    text = "\n".join(lines) + "\n"
+    print(text)
+    return text
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the table to this file")
+    ap.add_argument("--w4", action="store_true", help="W4 experts (moe_w4_gemm) beside the bf16 kernels")
     args = ap.parse_args()
     rows = [int(r) for r in os.getenv("ROWS", "1,16,64,256").split(",")]
     reps, iters = int(os.getenv("REPS", "5")), int(os.getenv("ITERS", "20"))
@@ -48,6 +100,13 @@ def main():
 
     router, wgu, wdown = draw(E, D, sd=0.02), draw(E, 2 * F, D, sd=0.02), draw(E, D, F, sd=0.02)
     ws = sops.MoeWorkspace(E, TOPK, D, F, dev)
+    if args.w4:
+        text = w4_table(dev, draw, router, wgu, wdown, ws, rows, reps, iters)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(text)
+        return
     lines = [f"# {torch.cuda.get_device_name(0)}; Mixtral-8x7B MoE MLP (hidden {D}, FFN {F}, {E} experts, top-{TOPK}); us per "
              f"call, median of {reps} x {iters} calls (min..max)",
              "# rows form split(gu,down) experts/call | gate/up moe_gemm us (spread)   GB/s | kernels MLP us (spread) | "
