@@ -124,6 +124,10 @@ bool dsa_moe_gemm_supported(int, int, int);
 int dsa_moe_gemm_split(int, int, int, int, int);
 hipError_t dsa_moe_gemm(const void*, long, int, int, const void*, const int*, const int*, float*, int, int, int, int, int,
                         int, hipStream_t);
+bool dsa_moe_fine_gemm_supported(int, int, int);
+int dsa_moe_fine_gemm_split(int, int, int, int, int);
+hipError_t dsa_moe_fine_gemm(const void*, long, int, int, const void*, const int*, const int*, float*, int, int, int, int,
+                             int, int, hipStream_t);
 int dsa_moe_w4_gemm_form(int);
 bool dsa_moe_w4_gemm_supported(int, int, int, int);
 int dsa_moe_w4_gemm_split(int, int, int, int, int);
@@ -837,9 +841,11 @@ void check_moe_rows(const torch::Tensor& x, int64_t cols, const char* what) {
               what, ": bf16 rows, contiguous and 16-byte aligned");
 }
 
-void check_moe_dims(int64_t R, int64_t k, int64_t E, const char* what) {
-  TORCH_CHECK(R >= 1 && R <= 256 && k >= 1 && k <= 8 && E >= k && E <= 64, what,
-              ": 1 <= rows <= 256, 1 <= experts per token <= 8, experts per token <= experts <= 64");
+// max_e: 64 for the grouped GEMMs of csrc/moe.hip and csrc/moe_w4.hip, 128 for the router, the lists and
+// csrc/moe_fine.hip
+void check_moe_dims(int64_t R, int64_t k, int64_t E, const char* what, int64_t max_e = 64) {
+  TORCH_CHECK(R >= 1 && R <= 256 && k >= 1 && k <= 8 && E >= k && E <= max_e, what,
+              ": 1 <= rows <= 256, 1 <= experts per token <= 8, experts per token <= experts <= ", max_e);
 }
 
 bool moe_gemm_supported(int64_t R, int64_t N, int64_t K) {
@@ -850,7 +856,7 @@ bool moe_gemm_supported(int64_t R, int64_t N, int64_t K) {
 void moe_lists(torch::Tensor topk_e, torch::Tensor live, torch::Tensor counts, torch::Tensor lists) {
   TORCH_CHECK(topk_e.dim() == 2 && counts.dim() == 1, "moe_lists: topk_e [R, k], counts [E]");
   const int64_t R = topk_e.size(0), k = topk_e.size(1), E = counts.size(0);
-  check_moe_dims(R, k, E, "moe_lists");
+  check_moe_dims(R, k, E, "moe_lists", 128);
   check_moe(topk_e, torch::kInt32, {R, k}, "moe_lists topk_e");
   check_moe(live, torch::kInt32, {R}, "moe_lists live");
   check_moe(counts, torch::kInt32, {E}, "moe_lists counts");
@@ -865,7 +871,7 @@ void moe_route(torch::Tensor h, torch::Tensor gate, torch::Tensor live, torch::T
                torch::Tensor counts, torch::Tensor lists) {
   TORCH_CHECK(h.dim() == 2 && gate.dim() == 2 && topk_e.dim() == 2, "moe_route: h [R, D], gate [E, D], topk_e [R, k]");
   const int64_t R = h.size(0), D = h.size(1), E = gate.size(0), k = topk_e.size(1);
-  check_moe_dims(R, k, E, "moe_route");
+  check_moe_dims(R, k, E, "moe_route", 128);
   TORCH_CHECK(D >= 8 && D % 8 == 0 && D <= INT_MAX, "moe_route: hidden size % 8 == 0");
   check_moe_rows(h, D, "moe_route h");
   check_moe(gate, torch::kBFloat16, {E, D}, "moe_route gate");
@@ -903,6 +909,36 @@ void moe_gemm(torch::Tensor x, int64_t src_div, torch::Tensor W, torch::Tensor c
                      lists.data_ptr<int>(), part.data_ptr<float>(), (int)R, (int)k, (int)E, (int)N, (int)K, (int)S,
                      stream()),
         "moe_gemm");
+}
+
+bool moe_fine_gemm_supported(int64_t R, int64_t N, int64_t K) {
+  return R <= INT_MAX && N <= INT_MAX && K <= INT_MAX && dsa_moe_fine_gemm_supported((int)R, (int)N, (int)K);
+}
+
+// moe_gemm's contract on the kernel for many small experts (csrc/moe_fine.hip): up to 128 experts, N % 128 == 0,
+// K slices of an even number >= 4 of 128-element steps
+void moe_fine_gemm(torch::Tensor x, int64_t src_div, torch::Tensor W, torch::Tensor counts, torch::Tensor lists,
+                   torch::Tensor part) {
+  TORCH_CHECK(x.dim() == 2 && W.dim() == 3 && lists.dim() == 2 && part.dim() == 3,
+              "moe_fine_gemm: x [rows, K], W [E, N, K], lists [E, R], part [S, R k, N]");
+  const int64_t E = W.size(0), N = W.size(1), K = W.size(2), R = lists.size(1), S = part.size(0), P = part.size(1);
+  TORCH_CHECK(R >= 1 && P % R == 0, "moe_fine_gemm: part holds R k rows per K slice");
+  const int64_t k = P / R;
+  check_moe_dims(R, k, E, "moe_fine_gemm", 128);
+  TORCH_CHECK(moe_fine_gemm_supported(R, N, K), "moe_fine_gemm: 1 <= R <= 256, N % 128 == 0, K % 256 == 0, K >= 512");
+  TORCH_CHECK(S >= 1 && K % S == 0 && (K / S) % 256 == 0 && K / S >= 512,
+              "moe_fine_gemm: K slices of an even number >= 4 of 128-element steps");
+  TORCH_CHECK((src_div == 1 || src_div == k) && x.size(0) * src_div == P,
+              "moe_fine_gemm: x has a row per pair (src_div 1) or per token row (src_div k)");
+  check_moe_rows(x, K, "moe_fine_gemm x");
+  check_moe(W, torch::kBFloat16, {E, N, K}, "moe_fine_gemm W");
+  check_moe(counts, torch::kInt32, {E}, "moe_fine_gemm counts");
+  check_moe(lists, torch::kInt32, {E, R}, "moe_fine_gemm lists");
+  check_moe(part, torch::kFloat32, {S, P, N}, "moe_fine_gemm part");
+  check(dsa_moe_fine_gemm(x.data_ptr(), x.stride(0), (int)x.size(0), (int)src_div, W.data_ptr(), counts.data_ptr<int>(),
+                          lists.data_ptr<int>(), part.data_ptr<float>(), (int)R, (int)k, (int)E, (int)N, (int)K, (int)S,
+                          stream()),
+        "moe_fine_gemm");
 }
 
 bool moe_w4_gemm_supported(int64_t R, int64_t N, int64_t K, int64_t g) {
@@ -1583,6 +1619,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return dsa_moe_gemm_split((int)R, (int)k, (int)E, (int)N, (int)K);
         },
         "K slices the MoE MLP runs this shape with (0: unsupported)");
+  m.def("moe_fine_gemm", &moe_fine_gemm, pybind11::arg("x"), pybind11::arg("src_div"), pybind11::arg("W"),
+        pybind11::arg("counts"), pybind11::arg("lists"), pybind11::arg("part"));
+  m.def("moe_fine_gemm_supported", &moe_fine_gemm_supported);
+  m.def("moe_fine_gemm_split",
+        [](int64_t R, int64_t k, int64_t E, int64_t N, int64_t K) {
+          return dsa_moe_fine_gemm_split((int)R, (int)k, (int)E, (int)N, (int)K);
+        },
+        "K slices moe_fine_gemm runs a shape with (0: unsupported)");
   m.def("moe_w4_gemm", &moe_w4_gemm, pybind11::arg("x"), pybind11::arg("src_div"), pybind11::arg("codes"),
         pybind11::arg("zeros"), pybind11::arg("scales"), pybind11::arg("N"), pybind11::arg("K"), pybind11::arg("g"),
         pybind11::arg("counts"), pybind11::arg("lists"), pybind11::arg("part"));

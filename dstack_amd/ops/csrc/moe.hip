@@ -38,21 +38,17 @@
 
 #include <type_traits>
 
-#include "stream_frag.h"
+#include "moe_frag.h"
 
 using namespace dsa;
-using stream::f32x4;
-using stream::i32x4;
+using namespace dsa::moe;
 
 namespace {
 
-constexpr int MOE_MAXR = 256;     // token rows
-constexpr int MOE_MAXE = 64;      // experts (one lane each in the router)
-constexpr int MOE_MAXK = 8;       // experts per token
-constexpr int MOE_BK = 128;       // K elements per step
+constexpr int MOE_MAXE = 64;      // experts of moe_gemm (one lane each in the router's first form)
+constexpr int MOE_MAXE2 = 128;    // experts of the router and the lists (two per lane in the router's second form)
 constexpr int MOE_WG_ROWS = 256;  // weight rows per workgroup
 constexpr int MOE_NWV = 8;        // waves
-constexpr int MOE_NF = 2;         // 16-row weight fragments per wave
 constexpr int MOE_UNROLL = 4;     // K-steps per K slice are a multiple of this (both ring sizes divide it)
 
 // ================================================================================================
@@ -119,6 +115,72 @@ __global__ __launch_bounds__(256) void moe_topk_kernel(const bf16_t* __restrict_
   }
 }
 
+// moe_better for candidates of up to 128 experts: an index >= 128 is out of the running
+__device__ __forceinline__ bool moe_better2(float av, int ai, float bv, int bi) {
+  const bool au = ai < 128, bu = bi < 128;
+  if (au != bu) return au;
+  return av > bv || (av == bv && ai < bi);
+}
+
+// The same rule for 64 < E <= 128: lane l of wave 0 holds experts l and l + 64.  A round first takes the
+// better of the lane's two candidates, then runs the wave's arg-max; the winner's probability comes from
+// the half of its lane that holds it.
+__global__ __launch_bounds__(256) void moe_topk2_kernel(const bf16_t* __restrict__ h, long ldh,
+                                                        const bf16_t* __restrict__ gate, int* __restrict__ topk_e,
+                                                        float* __restrict__ topk_w, int E, int k, int D) {
+  __shared__ float logit[MOE_MAXE2];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const bf16_t* x = h + (long)row * ldh;
+  for (int e = w; e < E; e += 4) {
+    const bf16_t* g = gate + (long)e * D;
+    float s = 0.f;
+    for (int c = lane * 8; c < D; c += 512) {
+      const us8 a = *reinterpret_cast<const us8*>(x + c), b = *reinterpret_cast<const us8*>(g + c);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s = __builtin_fmaf(bf2f(a[j]), bf2f(b[j]), s);
+    }
+    s = wave_sum(s);
+    if (lane == 0) logit[e] = s;
+  }
+  __syncthreads();
+  if (w != 0) return;
+  const bool valid1 = lane + 64 < E;  // (E > 64: expert `lane` exists in every lane)
+  const float l0 = logit[lane], l1 = valid1 ? logit[lane + 64] : -INFINITY;
+  const float key0 = (l0 != l0) ? -INFINITY : l0, key1 = (l1 != l1) ? -INFINITY : l1;
+  const float m = wave_max(fmaxf(l0, l1));  // (fmaxf drops a NaN)
+  float p0 = expf(l0 - m), p1 = valid1 ? expf(l1 - m) : 0.f;
+  const float z = wave_sum(p0 + p1);
+  p0 = p0 / z, p1 = p1 / z;
+  bool taken0 = false, taken1 = !valid1;
+  int my_e = 0;
+  float my_p = 0.f, sum = 0.f;
+  for (int j = 0; j < k; ++j) {
+    float bv = key0;
+    int bi = taken0 ? 128 + lane : lane;
+    const int ci = taken1 ? 192 + lane : 64 + lane;
+    if (moe_better2(key1, ci, bv, bi)) bv = key1, bi = ci;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (moe_better2(ov, oi, bv, bi)) bv = ov, bi = oi;
+    }
+    bi = min(bi & 127, E - 1);  // (k <= E: an expert is always left; in range whatever the bits)
+    const float a0 = __shfl(p0, bi & 63, 64), a1 = __shfl(p1, bi & 63, 64);
+    const float pj = bi < 64 ? a0 : a1;
+    if (lane == (bi & 63)) {
+      if (bi < 64) taken0 = true;
+      else taken1 = true;
+    }
+    if (lane == j) my_e = bi, my_p = pj;
+    sum += pj;
+  }
+  if (lane < k) {
+    topk_e[row * k + lane] = my_e;
+    topk_w[row * k + lane] = my_p / sum;
+  }
+}
+
 // One wave per expert: the pairs p = 0, 1, .. whose expert it is and whose row is live, in ascending
 // order, by ballots and prefix counts (no atomics: the order is the same every time).  The tail of
 // the list is -1.
@@ -143,19 +205,6 @@ __global__ __launch_bounds__(64) void moe_lists_kernel(const int* __restrict__ t
 // ================================================================================================
 // Grouped GEMM
 // ================================================================================================
-struct MoeArgs {
-  const bf16_t* X;    // bf16 [xrows][ldx]
-  const bf16_t* W;    // bf16 [E][N][K]
-  const int* counts;  // [E]
-  const int* lists;   // [E][R]
-  float* part;        // [S][P][N] fp32
-  long ldx;           // elements
-  int xrows, src_div, R, P, N, K, S;
-};
-
-// 16-byte chunk of a 256-byte activation row that holds K elements [8 c, 8 c + 8) of token `row`
-__device__ __forceinline__ int moe_chunk(int row, int c) { return c ^ (row & 15); }
-
 // XP 1 KiB activation pieces (4 tokens x 256 B) per wave and step; pieces past the last one are the
 // last one again (identical bytes to one slot), so every wave issues the same number of loads
 // (LB, TB: a tag per instantiation -- see the header of stream_frag.h)
@@ -167,29 +216,6 @@ __device__ __forceinline__ void moe_issue_x(__amdgpu_buffer_rsrc_t xrs, const un
     const int piece = min(w + MOE_NWV * i, 4 * LB - 1);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, LDS3(void, slot + piece * 1024), 16, xoff[i], so, 0, 0);
   }
-}
-
-// a lane's A operands of one K-step: per fragment four 16-byte pieces 64 bytes apart in its weight row
-template <int LB, int TB>
-__device__ __forceinline__ void moe_load_w(__amdgpu_buffer_rsrc_t wrs, const unsigned (&woff)[MOE_NF], int so,
-                                           i32x4 (&dst)[MOE_NF][4]) {
-#pragma unroll
-  for (int f = 0; f < MOE_NF; ++f)
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      const auto a = __builtin_amdgcn_raw_buffer_load_b128(wrs, (int)woff[f] + 64 * kk, so, 2);  // 2: nontemporal
-      dst[f][kk] = i32x4{(int)a[0], (int)a[1], (int)a[2], (int)a[3]};
-    }
-}
-
-// the 4 MFMA steps' B operands of one token block: token r (`row` points at it), K chunks 4 kk + gq
-__device__ __forceinline__ void moe_read_x(const char* row, int r, int gq, bf16x8 (&xf)[4]) {
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) xf[kk] = *reinterpret_cast<const bf16x8*>(row + moe_chunk(r, 4 * kk + gq) * 16);
-}
-
-__device__ __forceinline__ f32x4 moe_mfma(const i32x4& a, const bf16x8& b, const f32x4& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), b, c, 0, 0, 0);
 }
 
 // The K loop and the partial store of a workgroup whose expert e has cnt (1 .. 16 LB) pairs, with LB
@@ -402,7 +428,7 @@ extern "C" hipError_t dsa_moe_gemm(const void* X, long ldx, int xrows, int src_d
 // ================================================================================================
 extern "C" hipError_t dsa_moe_lists(const int* topk_e, const int* live, int* counts, int* lists, int R, int k, int E,
                                     hipStream_t st) {
-  if (R < 1 || R > MOE_MAXR || k < 1 || k > MOE_MAXK || E < k || E > MOE_MAXE) return hipErrorInvalidValue;
+  if (R < 1 || R > MOE_MAXR || k < 1 || k > MOE_MAXK || E < k || E > MOE_MAXE2) return hipErrorInvalidValue;
   moe_lists_kernel<<<E, 64, 0, st>>>(topk_e, live, counts, lists, R, k);
   return hipGetLastError();
 }
@@ -411,9 +437,12 @@ extern "C" hipError_t dsa_moe_lists(const int* topk_e, const int* live, int* cou
 extern "C" hipError_t dsa_moe_route(const void* h, long ldh, const void* gate, const int* live, int* topk_e,
                                     float* topk_w, int* counts, int* lists, int R, int k, int E, int D,
                                     hipStream_t st) {
-  if (R < 1 || R > MOE_MAXR || k < 1 || k > MOE_MAXK || E < k || E > MOE_MAXE || D < 8 || D % 8 || ldh % 8 || ldh < D)
+  if (R < 1 || R > MOE_MAXR || k < 1 || k > MOE_MAXK || E < k || E > MOE_MAXE2 || D < 8 || D % 8 || ldh % 8 || ldh < D)
     return hipErrorInvalidValue;
-  moe_topk_kernel<<<R, 256, 0, st>>>((const bf16_t*)h, ldh, (const bf16_t*)gate, topk_e, topk_w, E, k, D);
+  if (E <= MOE_MAXE)
+    moe_topk_kernel<<<R, 256, 0, st>>>((const bf16_t*)h, ldh, (const bf16_t*)gate, topk_e, topk_w, E, k, D);
+  else
+    moe_topk2_kernel<<<R, 256, 0, st>>>((const bf16_t*)h, ldh, (const bf16_t*)gate, topk_e, topk_w, E, k, D);
   DSA_CHECK(hipGetLastError());
   return dsa_moe_lists(topk_e, live, counts, lists, R, k, E, st);
 }

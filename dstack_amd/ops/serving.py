@@ -889,14 +889,16 @@ def w4_unshuffle(codes: torch.Tensor, zeros: torch.Tensor, scales: torch.Tensor,
 # Sparse mixture-of-experts MLP of the decode step: csrc/moe.hip
 # ----------------------------------------------------------------------------------------------
 MOE_MAX_ROWS = 256  # token rows the kernels take (a decode batch or a verify step)
-MOE_MAX_EXPERTS = 64
+MOE_MAX_EXPERTS = 64  # of the grouped GEMMs of csrc/moe.hip and csrc/moe_w4.hip (Mixtral)
+MOE_FINE_MAX_EXPERTS = 128  # of the router, the lists and csrc/moe_fine.hip (Qwen3-MoE)
 MOE_MAX_TOPK = 8
 
 
-def moe_check(E: int, k: int):
-    if not (1 <= k <= MOE_MAX_TOPK and k <= E <= MOE_MAX_EXPERTS):
-        raise ValueError(f"mixture of experts: {E} experts, {k} per token (num_local_experts: at most "
-                         f"{MOE_MAX_EXPERTS}; num_experts_per_tok: at most {MOE_MAX_TOPK} and no more than the experts)")
+def moe_check(E: int, k: int, max_experts: int = MOE_MAX_EXPERTS, field: str = "num_local_experts"):
+    """``max_experts``: the limit of the family's grouped GEMM; ``field``: how its config.json names the experts."""
+    if not (1 <= k <= MOE_MAX_TOPK and k <= E <= max_experts):
+        raise ValueError(f"mixture of experts: {E} experts, {k} per token ({field}: at most "
+                         f"{max_experts}; num_experts_per_tok: at most {MOE_MAX_TOPK} and no more than the experts)")
 
 
 def moe_route(h: torch.Tensor, gate: torch.Tensor, live: torch.Tensor, k: int, out=None):
@@ -907,7 +909,7 @@ def moe_route(h: torch.Tensor, gate: torch.Tensor, live: torch.Tensor, k: int, o
     if not _ext.use_hip(h):
         return moe_route_ref(h, gate, live, k)
     R, E = h.shape[0], gate.shape[0]
-    moe_check(E, k)
+    moe_check(E, k, MOE_FINE_MAX_EXPERTS)
     if out is None:
         i32 = dict(dtype=torch.int32, device=h.device)
         out = (torch.empty(R, k, **i32), torch.empty(R, k, dtype=torch.float32, device=h.device),
@@ -1005,15 +1007,24 @@ class MoeWorkspace:
     graph holds their addresses): routing, the fp32 split-K partials of the larger of the two GEMMs
     at its largest row count, and the per-pair activations."""
 
-    def __init__(self, E: int, k: int, D: int, F: int, device, w4_group: int | None = None):
+    def __init__(self, E: int, k: int, D: int, F: int, device, w4_group: int | None = None, fine: bool = False):
         """``w4_group``: the experts are W4 (:func:`moe_w4_mlp`) with this group size -- the shapes are
-        checked against ``moe_w4_gemm`` and the per-row split table comes from its rule."""
-        moe_check(E, k)
+        checked against ``moe_w4_gemm`` and the per-row split table comes from its rule.  ``fine``: the
+        workspace of :func:`moe_fine_mlp` -- up to 128 experts, the shapes checked against ``moe_fine_gemm``
+        and the splits from its rule."""
+        assert not (fine and w4_group is not None)
+        moe_check(E, k, MOE_FINE_MAX_EXPERTS if fine else MOE_MAX_EXPERTS, "num_experts" if fine else "num_local_experts")
         C = _ext.require()
-        if w4_group is None:
+        self.fine = fine
+        if fine:
+            ok, split = (lambda r, n, kk: C.moe_fine_gemm_supported(r, n, kk)), C.moe_fine_gemm_split
+        elif w4_group is None:
             ok, split = (lambda r, n, kk: C.moe_gemm_supported(r, n, kk)), C.moe_gemm_split
         else:
             ok, split = (lambda r, n, kk: C.moe_w4_gemm_supported(r, n, kk, w4_group)), C.moe_w4_gemm_split
+        if fine and not (ok(MOE_MAX_ROWS, 2 * F, D) and ok(MOE_MAX_ROWS, D, F)):
+            raise ValueError(f"mixture of experts: hidden size {D} and FFN size {F} must be multiples of 256 and at "
+                             "least 512 (the fine-grained expert GEMM's K-steps)")
         if not (ok(MOE_MAX_ROWS, 2 * F, D) and ok(MOE_MAX_ROWS, D, F)):
             raise ValueError(f"mixture of experts: hidden size {D} and FFN size {F} must be multiples of 512 (the "
                              "grouped decode GEMM's tiles)" + ("" if w4_group is None else
@@ -1081,6 +1092,45 @@ def _moe_mlp_eager(h, router, k, live, D, gate_up, down):
         a = _ext.require().swiglu_fwd(gu) if _ext.use_hip(gu) else ref.swiglu(gu)
         y.index_add_(0, rows, (a @ down(e).t()).float() * wflat[pairs][:, None])
     return y.to(h.dtype)
+
+
+# ----------------------------------------------------------------------------------------------
+# The same MLP over many small experts (Qwen3-MoE: 128 experts, 8 per token): csrc/moe_fine.hip
+# ----------------------------------------------------------------------------------------------
+def moe_fine_gemm_split(R: int, k: int, E: int, N: int, K: int) -> int:
+    """K slices the fine-grained expert GEMM runs a shape with, from the shape alone (0: unsupported)."""
+    return int(_ext.require().moe_fine_gemm_split(R, k, E, N, K))
+
+
+def moe_fine_gemm(x: torch.Tensor, src_div: int, W: torch.Tensor, counts: torch.Tensor, lists: torch.Tensor, split: int,
+                  part: torch.Tensor | None = None) -> torch.Tensor:
+    """:func:`moe_gemm` on the kernel for many small experts: up to 128 experts, ``W`` bf16 [E, N, K] with
+    N % 128 == 0 and every K slice (K / split) a multiple of 256 and at least 512; an expert with more
+    than 64 pairs is worked in passes.  Without the kernels: :func:`moe_gemm_ref`."""
+    if not _ext.use_hip(x):
+        return moe_gemm_ref(x, src_div, W, counts, lists, split)
+    if part is None:
+        part = torch.empty(split, x.shape[0] * src_div, W.shape[1], dtype=torch.float32, device=x.device)
+    _ext.require().moe_fine_gemm(x, src_div, W, counts, lists, part)
+    return part
+
+
+def moe_fine_mlp(h: torch.Tensor, router: torch.Tensor, wgu: torch.Tensor, wdown: torch.Tensor, k: int,
+                 live: torch.Tensor, ws: MoeWorkspace) -> torch.Tensor:
+    """:func:`moe_mlp` of up to 256 rows with :func:`moe_fine_gemm` between the same router, SwiGLU and
+    combine kernels.  Capturable.  ``ws``: a :class:`MoeWorkspace` made with ``fine=True``."""
+    assert ws.fine
+    R, E, D, F = h.shape[0], router.shape[0], ws.D, ws.F
+    if h.stride(-1) != 1 or h.stride(0) % 8 or h.data_ptr() % 16:
+        h = h.contiguous()
+    s1, s2 = ws.split[R]
+    P = R * k
+    topk_e, topk_w, counts, lists = moe_route(
+        h, router, live, k, out=(ws.topk_e[:P].view(R, k), ws.topk_w[:P].view(R, k), ws.counts, ws.lists[: E * R].view(E, R)))
+    part = moe_fine_gemm(h, k, wgu, counts, lists, s1, part=ws.part[: s1 * P * 2 * F].view(s1, P, 2 * F))
+    a = moe_swiglu(part, live, out=ws.a[:P])
+    part = moe_fine_gemm(a, 1, wdown, counts, lists, s2, part=ws.part[: s2 * P * D].view(s2, P, D))
+    return moe_combine(part, topk_w, live)
 
 
 # ----------------------------------------------------------------------------------------------

@@ -254,15 +254,23 @@ class ModelSpec:
     qk_norm: bool = False  # qwen3: per-head RMSNorm of q and k between the projection and RoPE
     head_dim: int | None = None  # where heads * head_dim is not hidden_size (qwen3); None: cfg.head_dim
     awq: AwqConfig | None = None  # the checkpoint's projections are AWQ 4-bit (config.json quantization_config)
-    n_experts: int = 0  # mixtral: experts per layer in place of the dense MLP (0: dense)
-    experts_per_tok: int = 0  # mixtral: experts the router picks per token
+    n_experts: int = 0  # mixtral, qwen3_moe: experts per layer in place of the dense MLP (0: dense)
+    experts_per_tok: int = 0  # mixtral, qwen3_moe: experts the router picks per token
 
 
-# sparse-MoE architectures with random weights (benchmarks): (block config, experts, experts per token)
+# sparse-MoE architectures with random weights (benchmarks): (block config, experts, experts per token, family)
 MOE_CONFIGS = {
     "mixtral-8x7b": (LlamaConfig(name="mixtral-8x7b", dim=4096, n_layers=32, n_heads=32, n_kv_heads=8, ffn_dim=14336,
-                                 vocab_size=32000, rope_theta=1e6, norm_eps=1e-5, max_seq_len=32768), 8, 2),
+                                 vocab_size=32000, rope_theta=1e6, norm_eps=1e-5, max_seq_len=32768), 8, 2, "mixtral"),
+    # (32 heads x 128 over a hidden size of 2048: ModelSpec.head_dim; ffn_dim is an expert's moe_intermediate_size)
+    "qwen3-30b-a3b": (LlamaConfig(name="qwen3-30b-a3b", dim=2048, n_layers=48, n_heads=32, n_kv_heads=4, ffn_dim=768,
+                                  vocab_size=151936, rope_theta=1e6, norm_eps=1e-6, max_seq_len=40960), 128, 8,
+                      "qwen3_moe"),
 }
+
+# per MoE family: (the most experts its grouped GEMM takes, the config.json field that counts them)
+MOE_FAMILIES = {"mixtral": (sops.MOE_MAX_EXPERTS, "num_local_experts"),
+                "qwen3_moe": (sops.MOE_FINE_MAX_EXPERTS, "num_experts")}
 
 
 def load_spec(model: str) -> ModelSpec:
@@ -272,13 +280,16 @@ def load_spec(model: str) -> ModelSpec:
     (q/k/v projection biases), Qwen3 dense (no biases; a per-head RMSNorm of q and k in front of RoPE,
     ``ModelSpec.qk_norm``; ``head_dim`` 128 from ``config.json`` with any ``hidden_size``,
     ``ModelSpec.head_dim``) and Mixtral (the Mistral block with ``num_local_experts`` experts behind a
-    router that picks ``num_experts_per_tok`` per token; ``mixtral-8x7b`` is built in).  A checkpoint whose ``config.json`` has a ``quantization_config`` must be
+    router that picks ``num_experts_per_tok`` per token; ``mixtral-8x7b`` is built in) and Qwen3-MoE (the
+    Qwen3 block with ``num_experts`` experts of ``moe_intermediate_size``; ``qwen3-30b-a3b`` is built in).  A checkpoint whose ``config.json`` has a ``quantization_config`` must be
     an AutoAWQ 4-bit "GEMM" one (``ModelSpec.awq``); anything else in it is an error naming the field."""
     if model in CONFIGS:
         return ModelSpec(CONFIGS[model], eos_token_ids=())
     if model in MOE_CONFIGS:
-        cfg, n_experts, per_tok = MOE_CONFIGS[model]
-        return ModelSpec(cfg, eos_token_ids=(), family="mixtral", n_experts=n_experts, experts_per_tok=per_tok)
+        cfg, n_experts, per_tok, family = MOE_CONFIGS[model]
+        qwen = family == "qwen3_moe"
+        return ModelSpec(cfg, eos_token_ids=(), family=family, n_experts=n_experts, experts_per_tok=per_tok,
+                         qk_norm=qwen, head_dim=128 if qwen else None)
     cfg_path = os.path.join(model, "config.json")
     if not os.path.exists(cfg_path):
         raise ValueError(f"unknown model {model!r}: neither a built-in config ({', '.join([*CONFIGS, *MOE_CONFIGS])}) "
@@ -292,11 +303,12 @@ def load_spec(model: str) -> ModelSpec:
     heads = hf["num_attention_heads"]
     dim = hf["hidden_size"]
     head_dim = hf.get("head_dim") or dim // heads
-    if family == "qwen3":  # the attention width heads * head_dim need not be hidden_size
+    qwen3 = family in ("qwen3", "qwen3_moe")  # (qwen3_moe: the qwen3 block with the MLP replaced by experts)
+    if qwen3:  # the attention width heads * head_dim need not be hidden_size
         if head_dim != 128:
             raise ValueError(f"head_dim must be 128 (got {head_dim})")
         if hf.get("attention_bias"):  # (false in every release; the loader has no place for the tensors)
-            raise ValueError("unsupported attention_bias=true in a qwen3 config.json (q/k/v/o biases)")
+            raise ValueError(f"unsupported attention_bias=true in a {family} config.json (q/k/v/o biases)")
     elif head_dim != 128 or dim != heads * head_dim:
         raise ValueError(f"head_dim must be 128 with hidden_size = heads * head_dim (got {head_dim})")
     # rope: ``rope_theta`` + ``rope_scaling`` (transformers 4.x) or ``rope_parameters`` (5.x)
@@ -312,7 +324,8 @@ def load_spec(model: str) -> ModelSpec:
         raise ValueError(f"unsupported activation {hf.get('hidden_act')} (SwiGLU / silu only)")
     cfg = LlamaConfig(
         name=os.path.basename(os.path.normpath(model)), dim=dim, n_layers=hf["num_hidden_layers"], n_heads=heads,
-        n_kv_heads=hf.get("num_key_value_heads", heads), ffn_dim=hf["intermediate_size"],
+        n_kv_heads=hf.get("num_key_value_heads", heads),
+        ffn_dim=hf["moe_intermediate_size" if family == "qwen3_moe" else "intermediate_size"],
         vocab_size=hf["vocab_size"], rope_theta=float(theta),
         norm_eps=float(hf.get("rms_norm_eps", 1e-5)), max_seq_len=max_len,
     )
@@ -333,20 +346,36 @@ def load_spec(model: str) -> ModelSpec:
     if family == "mixtral":  # the Mistral block with the MLP replaced by experts behind a linear router
         n_experts, per_tok = int(hf.get("num_local_experts", 8)), int(hf.get("num_experts_per_tok", 2))
         sops.moe_check(n_experts, per_tok)
+    if family == "qwen3_moe":  # every layer's MLP is experts, 8 of 128 per token with renormalized weights
+        n_experts = int(hf.get("num_experts", hf.get("num_local_experts", 128)))  # (transformers 5 writes the latter)
+        per_tok = int(hf.get("num_experts_per_tok", 8))
+        if not hf.get("norm_topk_prob", True):
+            raise ValueError("unsupported norm_topk_prob=false in a qwen3_moe config.json (the router kernel divides the "
+                             "chosen experts' probabilities by their sum)")
+        if hf.get("mlp_only_layers"):
+            raise ValueError(f"unsupported mlp_only_layers={hf['mlp_only_layers']} in a qwen3_moe config.json (dense "
+                             "layers among the sparse ones)")
+        if int(hf.get("decoder_sparse_step", 1)) != 1:
+            raise ValueError(f"unsupported decoder_sparse_step={hf['decoder_sparse_step']} in a qwen3_moe config.json "
+                             "(every layer must be sparse)")
+        sops.moe_check(n_experts, per_tok, *MOE_FAMILIES[family])
     return ModelSpec(cfg, scaling, bool(hf.get("tie_word_embeddings", False)), hf.get("bos_token_id"), eos_ids,
-                     path=model, family=family, qkv_bias=family == "qwen2", qk_norm=family == "qwen3",
-                     head_dim=head_dim if family == "qwen3" else None, awq=awq, n_experts=n_experts,
+                     path=model, family=family, qkv_bias=family == "qwen2", qk_norm=qwen3,
+                     head_dim=head_dim if qwen3 else None, awq=awq, n_experts=n_experts,
                      experts_per_tok=per_tok)
 
 
-SUPPORTED_FAMILIES = ("llama", "mistral", "qwen2", "qwen3", "mixtral")
+SUPPORTED_FAMILIES = ("llama", "mistral", "qwen2", "qwen3", "mixtral", "qwen3_moe")
 
 
 def check_moe(spec: ModelSpec, quantization: str | None, tensor_parallel: bool, lora_modules=None):
     """What a mixture-of-experts model cannot be combined with yet, each named by its option."""
     if not spec.n_experts:
         return
-    sops.moe_check(spec.n_experts, spec.experts_per_tok)
+    sops.moe_check(spec.n_experts, spec.experts_per_tok, *MOE_FAMILIES[spec.family])
+    if spec.family == "qwen3_moe" and quantization is not None:
+        raise ValueError(f"quantization={quantization!r} (--quantization) is not supported on a qwen3_moe model: its "
+                         "experts are served in bf16")
     if quantization not in (None, "awq"):
         raise ValueError(f"quantization={quantization!r} (--quantization) is not supported on a mixture-of-experts "
                          "model: its experts are served in bf16 or, from an AWQ checkpoint, in 4 bits")
@@ -417,8 +446,10 @@ class ServingLlama:
         self.E, self.topk = spec.n_experts, spec.experts_per_tok
         # (AWQ experts: the W4 grouped GEMM of csrc/moe_w4.hip, at the checkpoint's group size; 128 built in)
         self.moe_w4_group = (spec.awq.group_size if spec.awq else 128) if self.E and quantization == "awq" else None
-        self.moe_ws = sops.MoeWorkspace(self.E, self.topk, cfg.dim, cfg.ffn_dim, self.device,
-                                        w4_group=self.moe_w4_group) if self.E and self.hip else None
+        # (qwen3_moe, many small experts: the kernel of csrc/moe_fine.hip -- by family, not by shape)
+        self.moe_fine = bool(self.E) and spec.family == "qwen3_moe"
+        self.moe_ws = sops.MoeWorkspace(self.E, self.topk, cfg.dim, cfg.ffn_dim, self.device, w4_group=self.moe_w4_group,
+                                        fine=self.moe_fine) if self.E and self.hip else None
         self._moe_live = None  # int32 [rows] of the running step: > 0 where the row holds a token
         # DSTACK_AMD_GEMV=0: small decode batches on hipBLASLt too (A/B switch)
         self.gemv = os.environ.get("DSTACK_AMD_GEMV", "1") != "0"
@@ -643,6 +674,12 @@ class ServingLlama:
                             # the Hub's spelling: per expert w1 (gate) [F, D], w3 (up) [F, D], w2 (down) [D, F]
                             e = int(parts[5])
                             put({"w1": L["wgu"][e, :f], "w3": L["wgu"][e, f:], "w2": L["wdown"][e]}[parts[6]], t)
+                        elif self.E and len(parts) == 8 and parts[3:5] == ["mlp", "experts"] and parts[5].isdigit() \
+                                and int(parts[5]) < self.E and parts[6] in ("gate_proj", "up_proj", "down_proj") \
+                                and parts[7] == "weight":
+                            # Qwen3-MoE on the Hub: per expert gate_proj [F, D], up_proj [F, D], down_proj [D, F]
+                            e = int(parts[5])
+                            put({"gate_proj": L["wgu"][e, :f], "up_proj": L["wgu"][e, f:], "down_proj": L["wdown"][e]}[parts[6]], t)
                         elif self.E and key in ("mlp.experts.gate_up_proj", "mlp.experts.down_proj"):
                             # the fused spelling: [E, 2F, D] (gate rows first) and [E, D, F]; expert by expert
                             dst = L["wgu"] if key.endswith("gate_up_proj") else L["wdown"]
@@ -674,6 +711,10 @@ class ServingLlama:
                 expected |= {f"{pre}.gate.weight"} | {f"{pre}.experts.{e}.{w}.{kind}" for e in range(self.E)
                                                       for w in ("w1", "w2", "w3")
                                                       for kind in (self.AWQ_KINDS if awq else ("weight",))}
+            elif self.E and any(".mlp.experts.0." in n for n in seen):  # Qwen3-MoE's per-expert tensors
+                pre = f"model.layers.{i}.mlp"
+                expected |= {f"{pre}.gate.weight"} | {f"{pre}.experts.{e}.{w}.weight" for e in range(self.E)
+                                                      for w in ("gate_proj", "up_proj", "down_proj")}
             elif self.E:  # the fused tensors
                 expected |= {f"model.layers.{i}.mlp.{k}" for k in ("gate.weight", "experts.gate_up_proj", "experts.down_proj")}
             if self.spec.qkv_bias:
@@ -1243,7 +1284,10 @@ class ServingLlama:
         AWQ experts (``Awq4Experts``): up to 256 rows on the W4 grouped GEMM of ``csrc/moe_w4.hip``
         between the same router, SwiGLU and combine kernels (``sops.moe_w4_mlp``); more rows dequantize
         one expert at a time into the W4 scratch for the library GEMM pair (``sops.moe_w4_mlp_eager``);
-        CPU: ``ref.moe_mlp`` on the experts dequantized to fp32."""
+        CPU: ``ref.moe_mlp`` on the experts dequantized to fp32.
+
+        qwen3_moe (``self.moe_fine``): ``sops.moe_fine_mlp`` (``csrc/moe_fine.hip``) for every row count, a
+        prefill in chunks of 256 rows with ``live`` sliced alongside -- no host read on any path."""
         if isinstance(L["wgu"], Awq4Experts):
             wgu, wdown = L["wgu"], L["wdown"]
             if not self.hip:
@@ -1256,6 +1300,11 @@ class ServingLlama:
                                          self._w4_scratch)
         if not self.hip:
             return ref.moe_mlp(h, L["router"], L["wgu"], L["wdown"], self.topk, self._moe_live)
+        if self.moe_fine:  # every row count on the kernels, 256 rows at a time through the one workspace
+            n = sops.MOE_MAX_ROWS
+            ys = [sops.moe_fine_mlp(h[i : i + n], L["router"], L["wgu"], L["wdown"], self.topk, self._moe_live[i : i + n],
+                                    self.moe_ws) for i in range(0, h.shape[0], n)]
+            return ys[0] if len(ys) == 1 else torch.cat(ys)
         if h.shape[0] <= sops.MOE_MAX_ROWS:
             return sops.moe_mlp(h, L["router"], L["wgu"], L["wdown"], self.topk, self._moe_live, self.moe_ws)
         return sops.moe_mlp_eager(h, L["router"], L["wgu"], L["wdown"], self.topk, self._moe_live)

@@ -13,7 +13,12 @@ times after a warm-up; the spread is the min..max of a path's repetitions.
 ``moe_w4_gemm`` beside the bf16 ``moe_gemm`` on the same routing, for the gate/up and the down GEMM, and
 the whole MLP of both, alternating under the same protocol.
 
-    python tools/bench_moe.py [--w4] [--out FILE]  # ROWS=1,16,64,256 REPS=5 ITERS=20
+``--fine 30b`` / ``--fine 235b``: ``moe_fine_gemm`` (csrc/moe_fine.hip) at Qwen3-30B-A3B's shapes (hidden 2048,
+FFN 768, 128 experts, top-8) or at Qwen3-235B-A22B's (hidden 4096, FFN 1536) with 64 experts, top-8, which
+``moe_gemm`` can run too: there it runs beside ``moe_fine_gemm`` on the same routing.  Gate/up and down GEMM,
+the weight GB/s of the chosen experts, the whole MLP on the kernels against ``moe_mlp_eager``.
+
+    python tools/bench_moe.py [--w4 | --fine 30b|235b] [--out FILE]  # ROWS=1,16,64,256 REPS=5 ITERS=20
 """
 import argparse
 import os
@@ -85,9 +90,66 @@ def w4_table(dev, draw, router, wgu, wdown, ws, rows, reps, iters, g=128):
     return text
 
 
+FINE_SHAPES = {"30b": (128, 8, 2048, 768), "235b": (64, 8, 4096, 1536)}  # experts, top-k, hidden, FFN
+
+
+def fine_table(dev, draw, shape, rows, reps, iters):
+    E, TOPK, D, F = FINE_SHAPES[shape]
+    router, wgu, wdown = draw(E, D, sd=0.02), draw(E, 2 * F, D, sd=0.02), draw(E, D, F, sd=0.02)
+    ws = sops.MoeWorkspace(E, TOPK, D, F, dev, fine=True)
+    old = sops.MoeWorkspace(E, TOPK, D, F, dev) if E <= sops.MOE_MAX_EXPERTS else None  # moe_gemm beside it
+    lines = [f"# {torch.cuda.get_device_name(0)}; Qwen3-MoE MLP (hidden {D}, FFN {F}, {E} experts, top-{TOPK}); us per "
+             f"call, median of {reps} x {iters} calls (min..max)",
+             "# rows split(gu,down) experts/call | gate/up: fine us, GB/s" + (", moe_gemm us" if old else "")
+             + " | down: fine us, GB/s" + (", moe_gemm us" if old else "") + " | MLP: fine us"
+             + (", moe_gemm us" if old else "") + ", eager us, eager/fine"]
+    for R in rows:
+        hs = [draw(R, D, sd=1.0) for _ in range(8)]
+        acts = [draw(R * TOPK, F, sd=1.0) for _ in range(8)]
+        live = torch.ones(R, dtype=torch.int32, device=dev)
+        routed = [tuple(t.clone() for t in sops.moe_route(h, router, live, TOPK)) for h in hs]
+        chosen = statistics.mean(int((c > 0).sum()) for _, _, c, _ in routed)
+        P = R * TOPK
+
+        def part(w, s, n):
+            return w.part[: s * P * n].view(s, P, n)
+
+        s1, s2 = ws.split[R]
+        paths = {
+            "gu": lambda i: sops.moe_fine_gemm(hs[i % 8], TOPK, wgu, *routed[i % 8][2:], s1, part=part(ws, s1, 2 * F)),
+            "dn": lambda i: sops.moe_fine_gemm(acts[i % 8], 1, wdown, *routed[i % 8][2:], s2, part=part(ws, s2, D)),
+            "mlp": lambda i: sops.moe_fine_mlp(hs[i % 8], router, wgu, wdown, TOPK, live, ws),
+            "eager": lambda i: sops.moe_mlp_eager(hs[i % 8], router, wgu, wdown, TOPK, live),
+        }
+        if old:
+            b1, b2 = old.split[R]
+            paths["gu0"] = lambda i: sops.moe_gemm(hs[i % 8], TOPK, wgu, *routed[i % 8][2:], b1, part=part(old, b1, 2 * F))
+            paths["dn0"] = lambda i: sops.moe_gemm(acts[i % 8], 1, wdown, *routed[i % 8][2:], b2, part=part(old, b2, D))
+            paths["mlp0"] = lambda i: sops.moe_mlp(hs[i % 8], router, wgu, wdown, TOPK, live, old)
+        for fn in paths.values():
+            timed(fn, 8)
+        t = {name: [] for name in paths}
+        for _ in range(reps):
+            for name, fn in paths.items():
+                t[name].append(timed(fn, iters))
+        med = {name: statistics.median(v) for name, v in t.items()}
+        cell = {name: f"{med[name]:7.1f} ({min(v):.0f}..{max(v):.0f})" for name, v in t.items()}
+        gbs = {"gu": chosen * 2 * F * D * 2 / med["gu"] / 1e3, "dn": chosen * F * D * 2 / med["dn"] / 1e3}
+        lines.append(f"{R:6d} {s1},{s2} {chosen:6.1f} | "
+                     + " | ".join(f"{cell[a]} {gbs[a]:5.0f}" + (f" {cell[a + '0']}" if old else "") for a in ("gu", "dn"))
+                     + f" | {cell['mlp']}" + (f" {cell['mlp0']}" if old else "")
+                     + f" {cell['eager']} {med['eager'] / med['mlp']:.2f}x")
+        print(lines[-1], flush=True)
+    text = "\n".join(lines) + "\n"
+    print(text)
+    return text
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the table to this file")
+    ap.add_argument("--fine", choices=sorted(FINE_SHAPES), default=None,
+                    help="moe_fine_gemm at Qwen3-30B-A3B's shapes, or at Qwen3-235B's with 64 experts beside moe_gemm")
     ap.add_argument("--w4", action="store_true", help="W4 experts (moe_w4_gemm) beside the bf16 kernels")
     args = ap.parse_args()
     rows = [int(r) for r in os.getenv("ROWS", "1,16,64,256").split(",")]
@@ -98,10 +160,14 @@ def main():
     def draw(*shape, sd):
         return torch.empty(*shape, dtype=torch.bfloat16, device=dev).normal_(0.0, sd, generator=g)
 
-    router, wgu, wdown = draw(E, D, sd=0.02), draw(E, 2 * F, D, sd=0.02), draw(E, D, F, sd=0.02)
-    ws = sops.MoeWorkspace(E, TOPK, D, F, dev)
-    if args.w4:
+    if args.fine:
+        text = fine_table(dev, draw, args.fine, rows, reps, iters)
+    else:
+        router, wgu, wdown = draw(E, D, sd=0.02), draw(E, 2 * F, D, sd=0.02), draw(E, D, F, sd=0.02)
+        ws = sops.MoeWorkspace(E, TOPK, D, F, dev)
+    if args.w4 and not args.fine:
         text = w4_table(dev, draw, router, wgu, wdown, ws, rows, reps, iters)
+    if args.w4 or args.fine:
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:
