@@ -828,17 +828,19 @@ torch::Tensor w4_dequant(torch::Tensor wc, torch::Tensor wz, torch::Tensor wsc, 
 }
 
 // ---- sparse mixture-of-experts MLP of the decode step (csrc/moe.hip); every output is the caller's ----
-void check_moe(const torch::Tensor& t, torch::ScalarType ty, std::initializer_list<int64_t> shape, const char* what) {
+// (what, of: the two halves of the tensor's name in the message)
+void check_moe(const torch::Tensor& t, torch::ScalarType ty, std::initializer_list<int64_t> shape, const char* what,
+               const char* of = "") {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == ty && t.is_contiguous() && t.sizes() == torch::IntArrayRef(shape) &&
                   reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
-              what, ": a contiguous, 16-byte aligned ROCm tensor of the documented dtype and shape");
+              what, of, ": a contiguous, 16-byte aligned ROCm tensor of the documented dtype and shape");
 }
 
-void check_moe_rows(const torch::Tensor& x, int64_t cols, const char* what) {
+void check_moe_rows(const torch::Tensor& x, int64_t cols, const char* what, const char* of = "") {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 && x.dim() == 2 && x.size(1) == cols &&
                   x.stride(1) == 1 && x.stride(0) % 8 == 0 && x.stride(0) >= cols &&
                   reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
-              what, ": bf16 rows, contiguous and 16-byte aligned");
+              what, of, ": bf16 rows, contiguous and 16-byte aligned");
 }
 
 // max_e: 64 for the grouped GEMMs of csrc/moe.hip and csrc/moe_w4.hip, 128 for the router, the lists and
@@ -886,25 +888,40 @@ void moe_route(torch::Tensor h, torch::Tensor gate, torch::Tensor live, torch::T
         "moe_route");
 }
 
+struct MoeGemmDims {
+  int64_t R, k, E, S, P;
+};
+
+// What moe_gemm, moe_fine_gemm and moe_w4_gemm (`op`) check alike: x bf16 [R k / src_div, K], w the weight [E,
+// ..] (`wshape`: how the message writes it, of at most max_e experts), counts [E], lists [E, R], part fp32 [S, R k,
+// N].  The caller checks what its kernel asks of R, N, K and S, and its weight tensors.
+MoeGemmDims check_moe_gemm(const char* op, const char* wshape, int64_t max_e, const torch::Tensor& x,
+                           int64_t src_div, const torch::Tensor& w, int64_t N, int64_t K, const torch::Tensor& counts,
+                           const torch::Tensor& lists, const torch::Tensor& part) {
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 3 && lists.dim() == 2 && part.dim() == 3, op, ": x [rows, K], ", wshape,
+              ", lists [E, R], part [S, R k, N]");
+  const int64_t E = w.size(0), R = lists.size(1), S = part.size(0), P = part.size(1);
+  TORCH_CHECK(R >= 1 && P % R == 0, op, ": part holds R k rows per K slice");
+  const int64_t k = P / R;
+  check_moe_dims(R, k, E, op, max_e);
+  TORCH_CHECK((src_div == 1 || src_div == k) && x.size(0) * src_div == P, op,
+              ": x has a row per pair (src_div 1) or per token row (src_div k)");
+  check_moe_rows(x, K, op, " x");
+  check_moe(counts, torch::kInt32, {E}, op, " counts");
+  check_moe(lists, torch::kInt32, {E, R}, op, " lists");
+  check_moe(part, torch::kFloat32, {S, P, N}, op, " part");
+  return {R, k, E, S, P};
+}
+
 // part[s][p][:] = x[p / src_div] W[expert(p)]^T over K slice s: x bf16 [R k / src_div, K], W bf16 [E, N, K],
 // counts [E], lists [E, R], part fp32 [S, R k, N]
 void moe_gemm(torch::Tensor x, int64_t src_div, torch::Tensor W, torch::Tensor counts, torch::Tensor lists,
               torch::Tensor part) {
-  TORCH_CHECK(x.dim() == 2 && W.dim() == 3 && lists.dim() == 2 && part.dim() == 3,
-              "moe_gemm: x [rows, K], W [E, N, K], lists [E, R], part [S, R k, N]");
-  const int64_t E = W.size(0), N = W.size(1), K = W.size(2), R = lists.size(1), S = part.size(0), P = part.size(1);
-  TORCH_CHECK(R >= 1 && P % R == 0, "moe_gemm: part holds R k rows per K slice");
-  const int64_t k = P / R;
-  check_moe_dims(R, k, E, "moe_gemm");
+  const int64_t N = W.dim() == 3 ? W.size(1) : 0, K = W.dim() == 3 ? W.size(2) : 0;  // (another W: refused below)
+  const auto [R, k, E, S, P] = check_moe_gemm("moe_gemm", "W [E, N, K]", 64, x, src_div, W, N, K, counts, lists, part);
   TORCH_CHECK(moe_gemm_supported(R, N, K), "moe_gemm: 1 <= R <= 256, N % 256 == 0, K % 512 == 0");
   TORCH_CHECK(S >= 1 && K % (512 * S) == 0, "moe_gemm: K slices of whole 512-element groups");
-  TORCH_CHECK((src_div == 1 || src_div == k) && x.size(0) * src_div == P,
-              "moe_gemm: x has a row per pair (src_div 1) or per token row (src_div k)");
-  check_moe_rows(x, K, "moe_gemm x");
   check_moe(W, torch::kBFloat16, {E, N, K}, "moe_gemm W");
-  check_moe(counts, torch::kInt32, {E}, "moe_gemm counts");
-  check_moe(lists, torch::kInt32, {E, R}, "moe_gemm lists");
-  check_moe(part, torch::kFloat32, {S, P, N}, "moe_gemm part");
   check(dsa_moe_gemm(x.data_ptr(), x.stride(0), (int)x.size(0), (int)src_div, W.data_ptr(), counts.data_ptr<int>(),
                      lists.data_ptr<int>(), part.data_ptr<float>(), (int)R, (int)k, (int)E, (int)N, (int)K, (int)S,
                      stream()),
@@ -919,22 +936,13 @@ bool moe_fine_gemm_supported(int64_t R, int64_t N, int64_t K) {
 // K slices of an even number >= 4 of 128-element steps
 void moe_fine_gemm(torch::Tensor x, int64_t src_div, torch::Tensor W, torch::Tensor counts, torch::Tensor lists,
                    torch::Tensor part) {
-  TORCH_CHECK(x.dim() == 2 && W.dim() == 3 && lists.dim() == 2 && part.dim() == 3,
-              "moe_fine_gemm: x [rows, K], W [E, N, K], lists [E, R], part [S, R k, N]");
-  const int64_t E = W.size(0), N = W.size(1), K = W.size(2), R = lists.size(1), S = part.size(0), P = part.size(1);
-  TORCH_CHECK(R >= 1 && P % R == 0, "moe_fine_gemm: part holds R k rows per K slice");
-  const int64_t k = P / R;
-  check_moe_dims(R, k, E, "moe_fine_gemm", 128);
+  const int64_t N = W.dim() == 3 ? W.size(1) : 0, K = W.dim() == 3 ? W.size(2) : 0;  // (another W: refused below)
+  const auto [R, k, E, S, P] =
+      check_moe_gemm("moe_fine_gemm", "W [E, N, K]", 128, x, src_div, W, N, K, counts, lists, part);
   TORCH_CHECK(moe_fine_gemm_supported(R, N, K), "moe_fine_gemm: 1 <= R <= 256, N % 128 == 0, K % 256 == 0, K >= 512");
   TORCH_CHECK(S >= 1 && K % S == 0 && (K / S) % 256 == 0 && K / S >= 512,
               "moe_fine_gemm: K slices of an even number >= 4 of 128-element steps");
-  TORCH_CHECK((src_div == 1 || src_div == k) && x.size(0) * src_div == P,
-              "moe_fine_gemm: x has a row per pair (src_div 1) or per token row (src_div k)");
-  check_moe_rows(x, K, "moe_fine_gemm x");
   check_moe(W, torch::kBFloat16, {E, N, K}, "moe_fine_gemm W");
-  check_moe(counts, torch::kInt32, {E}, "moe_fine_gemm counts");
-  check_moe(lists, torch::kInt32, {E, R}, "moe_fine_gemm lists");
-  check_moe(part, torch::kFloat32, {S, P, N}, "moe_fine_gemm part");
   check(dsa_moe_fine_gemm(x.data_ptr(), x.stride(0), (int)x.size(0), (int)src_div, W.data_ptr(), counts.data_ptr<int>(),
                           lists.data_ptr<int>(), part.data_ptr<float>(), (int)R, (int)k, (int)E, (int)N, (int)K, (int)S,
                           stream()),
@@ -949,24 +957,14 @@ bool moe_w4_gemm_supported(int64_t R, int64_t N, int64_t K, int64_t g) {
 // fp16 [E, N, K/g], every expert in ops.serving.w4_shuffle's stored form; the rest as moe_gemm
 void moe_w4_gemm(torch::Tensor x, int64_t src_div, torch::Tensor wc, torch::Tensor wz, torch::Tensor wsc, int64_t N,
                  int64_t K, int64_t g, torch::Tensor counts, torch::Tensor lists, torch::Tensor part) {
-  TORCH_CHECK(x.dim() == 2 && wc.dim() == 3 && lists.dim() == 2 && part.dim() == 3,
-              "moe_w4_gemm: x [rows, K], codes [E, N, K/2], lists [E, R], part [S, R k, N]");
-  const int64_t E = wc.size(0), R = lists.size(1), S = part.size(0), P = part.size(1);
-  TORCH_CHECK(R >= 1 && P % R == 0, "moe_w4_gemm: part holds R k rows per K slice");
-  const int64_t k = P / R;
-  check_moe_dims(R, k, E, "moe_w4_gemm");
+  const auto [R, k, E, S, P] =
+      check_moe_gemm("moe_w4_gemm", "codes [E, N, K/2]", 64, x, src_div, wc, N, K, counts, lists, part);
   TORCH_CHECK(moe_w4_gemm_supported(R, N, K, g),
               "moe_w4_gemm: 1 <= R <= 256, N % 256 == 0, K % 512 == 0, group size 32, 64 or 128");
   TORCH_CHECK(S >= 1 && K % (512 * S) == 0, "moe_w4_gemm: K slices of whole 512-element groups");
-  TORCH_CHECK((src_div == 1 || src_div == k) && x.size(0) * src_div == P,
-              "moe_w4_gemm: x has a row per pair (src_div 1) or per token row (src_div k)");
-  check_moe_rows(x, K, "moe_w4_gemm x");
   check_moe(wc, torch::kUInt8, {E, N, K / 2}, "moe_w4_gemm codes");
   check_moe(wz, torch::kUInt8, {E, N, K / g}, "moe_w4_gemm zeros");
   check_moe(wsc, torch::kFloat16, {E, N, K / g}, "moe_w4_gemm scales");
-  check_moe(counts, torch::kInt32, {E}, "moe_w4_gemm counts");
-  check_moe(lists, torch::kInt32, {E, R}, "moe_w4_gemm lists");
-  check_moe(part, torch::kFloat32, {S, P, N}, "moe_w4_gemm part");
   check(dsa_moe_w4_gemm(x.data_ptr(), x.stride(0), (int)x.size(0), (int)src_div, wc.data_ptr(), wz.data_ptr(),
                         wsc.data_ptr(), counts.data_ptr<int>(), lists.data_ptr<int>(), part.data_ptr<float>(), (int)R,
                         (int)k, (int)E, (int)N, (int)K, (int)g, (int)S, stream()),

@@ -34,11 +34,15 @@
 //
 // Every index read from memory (counts, lists, topk_e) is clamped to its range before it addresses
 // anything, so no input bits can take an access out of bounds.
+//
+// Device code shared with moe_fine.hip: moe_frag.h.  Launch code shared with moe_fine.hip and moe_w4.hip
+// (the form ladder, the check of x, the rule for the K slices, the launch): moe_host.h.
 #include <stdint.h>
 
 #include <type_traits>
 
 #include "moe_frag.h"
+#include "moe_host.h"
 
 using namespace dsa;
 using namespace dsa::moe;
@@ -363,8 +367,7 @@ __global__ __launch_bounds__(64 * MOE_NWV, 1) void moe_gemm_kernel(MoeArgs p) {
   moe_body<1, TB>(p, smem, e, cnt);
 }
 
-// 16-token blocks of the form that runs R rows: 1 (R <= 16), 2, 4, 8, 16
-extern "C" int dsa_moe_gemm_form(int R) { return R <= 16 ? 1 : R <= 32 ? 2 : R <= 64 ? 4 : R <= 128 ? 8 : 16; }
+extern "C" int dsa_moe_gemm_form(int R) { return moe_host_form(R); }
 
 extern "C" bool dsa_moe_gemm_supported(int R, int N, int K) {
   // 256 weight rows per workgroup; K slices of 4 whole K-steps; an expert's weight through a 32-bit
@@ -373,34 +376,20 @@ extern "C" bool dsa_moe_gemm_supported(int R, int N, int K) {
          (long)N * K * 2 <= 0xffffffffL;
 }
 
-// K slices, from the shape alone (a launch inside a captured graph cannot look at the counts): the most
-// that divide K / 512, keep the grid of the experts that min(E, R k) pairs can reach within two
-// workgroups per CU, and keep the fp32 partials (written and read once) under a quarter of those
-// experts' weight bytes: S * R k * N * 8 <= active * N * K * 2 / 4
+// a K slice the loop can run: whole groups of 4 K-steps
+static bool moe_slices(int K, int S) { return S >= 1 && K % (MOE_BK * MOE_UNROLL * S) == 0; }
+
+// K slices: moe_host_split's rule with 256-row tiles and 2 bytes per weight
 extern "C" int dsa_moe_gemm_split(int R, int k, int E, int N, int K) {
   if (!dsa_moe_gemm_supported(R, N, K) || k < 1 || k > MOE_MAXK || E < k || E > MOE_MAXE) return 0;
-  const int groups = K / (MOE_BK * MOE_UNROLL), wgs = N / MOE_WG_ROWS;
-  const long active = (long)R * k < E ? (long)R * k : E;
-  int best = 1;
-  for (int s = 2; s <= groups && s <= 16; ++s)
-    if (groups % s == 0 && wgs * active * s <= 512 && (long)s * R * k * 16 <= active * K) best = s;
-  return best;
+  return moe_host_split(R, k, E, N / MOE_WG_ROWS, K, 2, 1, [K](int s) { return moe_slices(K, s); });
 }
 
-namespace {
 template <int TB>
-hipError_t moe_launch(const MoeArgs& a, int E, hipStream_t st) {
-  constexpr int LDS = (TB >= 16 ? 2 : 4) * TB * 4096;
-  static bool attr = false;
-  if (!attr) {
-    DSA_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&moe_gemm_kernel<TB>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    attr = true;
-  }
-  moe_gemm_kernel<TB><<<dim3(a.N / MOE_WG_ROWS, E, a.S), 64 * MOE_NWV, LDS, st>>>(a);
-  return hipGetLastError();
+static hipError_t moe_launch(const MoeArgs& a, int E, hipStream_t st) {
+  return moe_host_launch<&moe_gemm_kernel<TB>, (TB >= 16 ? 2 : 4) * TB * 4096>(dim3(a.N / MOE_WG_ROWS, E, a.S),
+                                                                                64 * MOE_NWV, a, st);
 }
-}  // namespace
 
 // part[s][p][:] = X[p / src_div] W[expert(p)]^T over K slice s, for every pair p in the experts' lists:
 // X bf16 [xrows][K] (row stride ldx elements), W bf16 [E][N][K], counts [E], lists [E][R] (moe_route),
@@ -409,12 +398,9 @@ extern "C" hipError_t dsa_moe_gemm(const void* X, long ldx, int xrows, int src_d
                                    const int* lists, float* part, int R, int k, int E, int N, int K, int S,
                                    hipStream_t st) {
   if (!dsa_moe_gemm_supported(R, N, K) || k < 1 || k > MOE_MAXK || E < k || E > MOE_MAXE) return hipErrorInvalidValue;
-  if (S < 1 || K % (MOE_BK * MOE_UNROLL * S) || part == nullptr) return hipErrorInvalidValue;
-  if (ldx % 8 || ldx < K || src_div < 1 || xrows < 1 || (long)xrows * src_div < (long)R * k)
-    return hipErrorInvalidValue;
-  if (((long)(xrows - 1) * ldx + K) * 2 > 0xffffffffL) return hipErrorInvalidValue;  // X through a 32-bit buffer range
+  if (!moe_slices(K, S) || part == nullptr || !moe_host_x_ok(ldx, xrows, src_div, R, k, K)) return hipErrorInvalidValue;
   MoeArgs a{(const bf16_t*)X, (const bf16_t*)W, counts, lists, part, ldx, xrows, src_div, R, R * k, N, K, S};
-  switch (dsa_moe_gemm_form(R)) {
+  switch (moe_host_form(R)) {
     case 1: return moe_launch<1>(a, E, st);
     case 2: return moe_launch<2>(a, E, st);
     case 4: return moe_launch<4>(a, E, st);

@@ -32,8 +32,8 @@
 // Chosen: 128-row tiles (Qwen3-30B-A3B's down projection has N = 2048: 16 tiles x 8 chosen experts is
 // 128 workgroups for one token, half the CUs; 256-row tiles would halve that again), a ring four deep
 // for every form (6-step loops spend half their time in prologue and drain at any depth; 4 keeps three
-// loads in flight per lane and fragment), K slices by moe_gemm's rule with this kernel's tile and step
-// constraints (dsa_moe_fine_gemm_split).  Not tried: 64-row tiles, 2 waves x 4 fragments, 8-block
+// loads in flight per lane and fragment), K slices by moe_gemm's rule (moe_host.h) with this kernel's tile
+// and step constraints (dsa_moe_fine_gemm_split).  Not tried: 64-row tiles, 2 waves x 4 fragments, 8-block
 // passes with one workgroup per CU, a narrower tile at row counts where few experts are hit, keeping a
 // multi-pass expert's weights in registers or LDS instead of re-reading them.
 #include <stdint.h>
@@ -41,6 +41,7 @@
 #include <type_traits>
 
 #include "moe_frag.h"
+#include "moe_host.h"
 
 using namespace dsa;
 using namespace dsa::moe;
@@ -228,33 +229,16 @@ extern "C" bool dsa_moe_fine_gemm_supported(int R, int N, int K) {
 // a K slice the loop can run: an even number >= 4 of whole steps
 static bool fine_slices(int K, int S) { return S >= 1 && K % S == 0 && (K / S) % (2 * MOE_BK) == 0 && K / S >= 4 * MOE_BK; }
 
-// K slices, from the shape alone (a launch inside a captured graph cannot look at the counts): moe_gemm's
-// rule with this kernel's tile -- the most that the loop can run, that keep the grid of the experts that
-// min(E, R k) pairs can reach within two workgroups per CU, and that keep the fp32 partials (written and
-// read once) under a quarter of those experts' weight bytes: S * R k * N * 8 <= active * N * K * 2 / 4
+// K slices: moe_host_split's rule with 128-row tiles and 2 bytes per weight
 extern "C" int dsa_moe_fine_gemm_split(int R, int k, int E, int N, int K) {
   if (!dsa_moe_fine_gemm_supported(R, N, K) || k < 1 || k > MOE_MAXK || E < k || E > FINE_MAXE) return 0;
-  const int wgs = N / FINE_WG_ROWS;
-  const long active = (long)R * k < E ? (long)R * k : E;
-  int best = 1;
-  for (int s = 2; s <= 16; ++s)
-    if (fine_slices(K, s) && wgs * active * s <= 512 && (long)s * R * k * 16 <= active * K) best = s;
-  return best;
+  return moe_host_split(R, k, E, N / FINE_WG_ROWS, K, 2, 1, [K](int s) { return fine_slices(K, s); });
 }
 
-namespace {
 template <bool SIX>
-hipError_t fine_launch(const MoeArgs& a, int E, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    DSA_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&moe_fine_gemm_kernel<SIX>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, FINE_LDS));
-    attr = true;
-  }
-  moe_fine_gemm_kernel<SIX><<<dim3(a.N / FINE_WG_ROWS, E, a.S), 64 * FINE_NWV, FINE_LDS, st>>>(a);
-  return hipGetLastError();
+static hipError_t fine_launch(const MoeArgs& a, int E, hipStream_t st) {
+  return moe_host_launch<&moe_fine_gemm_kernel<SIX>, FINE_LDS>(dim3(a.N / FINE_WG_ROWS, E, a.S), 64 * FINE_NWV, a, st);
 }
-}  // namespace
 
 // part[s][p][:] = X[p / src_div] W[expert(p)]^T over K slice s, for every pair p in the experts' lists:
 // X bf16 [xrows][K] (row stride ldx elements), W bf16 [E][N][K], counts [E], lists [E][R] (moe_route),
@@ -263,10 +247,7 @@ extern "C" hipError_t dsa_moe_fine_gemm(const void* X, long ldx, int xrows, int 
                                         const int* lists, float* part, int R, int k, int E, int N, int K, int S,
                                         hipStream_t st) {
   if (!dsa_moe_fine_gemm_supported(R, N, K) || k < 1 || k > MOE_MAXK || E < k || E > FINE_MAXE) return hipErrorInvalidValue;
-  if (!fine_slices(K, S) || part == nullptr) return hipErrorInvalidValue;
-  if (ldx % 8 || ldx < K || src_div < 1 || xrows < 1 || (long)xrows * src_div < (long)R * k)
-    return hipErrorInvalidValue;
-  if (((long)(xrows - 1) * ldx + K) * 2 > 0xffffffffL) return hipErrorInvalidValue;  // X through a 32-bit buffer range
+  if (!fine_slices(K, S) || part == nullptr || !moe_host_x_ok(ldx, xrows, src_div, R, k, K)) return hipErrorInvalidValue;
   MoeArgs a{(const bf16_t*)X, (const bf16_t*)W, counts, lists, part, ldx, xrows, src_div, R, R * k, N, K, S};
   return (K / S / MOE_BK) & 2 ? fine_launch<true>(a, E, st) : fine_launch<false>(a, E, st);
 }

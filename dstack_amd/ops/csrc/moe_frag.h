@@ -2,7 +2,8 @@
 // moe_fine.hip: moe_fine_gemm, many small ones): the argument block, the swizzle of the activation
 // ring, a lane's weight loads of one K-step, the B-operand reads of one token block and the MFMA.
 // Each file keeps its own tile, wave count, ring depth, K loop and activation issue.  moe_load_w
-// carries a tag per instantiation (see the header of stream_frag.h).
+// carries a tag per instantiation (see the header of stream_frag.h).  Device code only: what the
+// launch code of these two and of moe_w4.hip shares is in moe_host.h.
 #pragma once
 
 #include "stream_frag.h"

@@ -35,7 +35,8 @@
 //    moe_combine: no atomics, the same inputs give the same bits.
 //
 // Every index read from memory (counts, lists) is clamped to its range before it addresses anything,
-// and every weight and activation load goes through a descriptor sized to its array.
+// and every weight and activation load goes through a descriptor sized to its array.  The form ladder,
+// the check of x, the rule for the K slices and the launch are moe_gemm's: moe_host.h.
 //
 // Registers, from the build's metadata (-Rpass-analysis=kernel-resource-usage; 512 threads, so 256
 // registers per lane).  A kernel of form TB holds the bodies of every LB <= TB, so its figures cover
@@ -48,6 +49,7 @@
 #include <type_traits>
 
 #include "w4_frag.h"
+#include "moe_host.h"
 
 using namespace dsa;
 using namespace dsa::w4;
@@ -335,8 +337,7 @@ __global__ __launch_bounds__(64 * MW4_NWV, 1) void moe_w4_gemm_kernel(MoeW4Args 
   mw4_body<1, TB, GS>(p, smem, e, cnt);
 }
 
-// 16-token blocks of the form that runs R rows: 1 (R <= 16), 2, 4, 8, 16
-extern "C" int dsa_moe_w4_gemm_form(int R) { return R <= 16 ? 1 : R <= 32 ? 2 : R <= 64 ? 4 : R <= 128 ? 8 : 16; }
+extern "C" int dsa_moe_w4_gemm_form(int R) { return moe_host_form(R); }
 
 extern "C" bool dsa_moe_w4_gemm_supported(int R, int N, int K, int g) {
   // 256 weight rows per workgroup; K slices of 4 whole K-steps; an expert's codes through a 32-bit
@@ -345,38 +346,26 @@ extern "C" bool dsa_moe_w4_gemm_supported(int R, int N, int K, int g) {
          (g == 32 || g == 64 || g == 128) && (long)N * K / 2 <= 0xffffffffL;
 }
 
-// K slices, from the shape alone (a launch inside a captured graph cannot look at the counts):
-// dsa_moe_gemm_split's rule with the weight bytes of W4 (0.52 per weight at g = 128) -- the most that
-// divide K / 512, keep the grid of the experts that min(E, R k) pairs can reach within two workgroups
-// per CU, and keep the fp32 partials (written and read once) under a quarter of those experts' weight
-// bytes: S * R k * N * 8 <= active * N * K * 0.52 / 4
+// a K slice the loop can run: whole groups of 4 K-steps
+static bool mw4_slices(int K, int S) { return S >= 1 && K % (MW4_BK * MW4_UNROLL * S) == 0; }
+
+// K slices: moe_host_split's rule with 256-row tiles and the weight bytes of W4 at g = 128, 0.52 = 13 / 25
+// per weight
 extern "C" int dsa_moe_w4_gemm_split(int R, int k, int E, int N, int K) {
   if (!dsa_moe_w4_gemm_supported(R, N, K, 128) || k < 1 || k > MW4_MAXK || E < k || E > MW4_MAXE) return 0;
-  const int groups = K / (MW4_BK * MW4_UNROLL), wgs = N / MW4_WG_ROWS;
-  const long active = (long)R * k < E ? (long)R * k : E;
-  int best = 1;
-  for (int s = 2; s <= groups && s <= 16; ++s)
-    if (groups % s == 0 && wgs * active * s <= 512 && (long)s * R * k * 800 <= active * K * 13) best = s;
-  return best;
+  return moe_host_split(R, k, E, N / MW4_WG_ROWS, K, 13, 25, [K](int s) { return mw4_slices(K, s); });
 }
 
 namespace {
 template <int TB, int GS>
 hipError_t mw4_launch(const MoeW4Args& a, int E, hipStream_t st) {
-  constexpr int LDS = mw4_slots(TB, GS) * TB * 4096;
-  static bool attr = false;
-  if (!attr) {
-    DSA_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&moe_w4_gemm_kernel<TB, GS>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    attr = true;
-  }
-  moe_w4_gemm_kernel<TB, GS><<<dim3(a.N / MW4_WG_ROWS, E, a.S), 64 * MW4_NWV, LDS, st>>>(a);
-  return hipGetLastError();
+  return moe_host_launch<&moe_w4_gemm_kernel<TB, GS>, mw4_slots(TB, GS) * TB * 4096>(dim3(a.N / MW4_WG_ROWS, E, a.S),
+                                                                                      64 * MW4_NWV, a, st);
 }
 
 template <int GS>
 hipError_t mw4_launch_form(const MoeW4Args& a, int E, hipStream_t st) {
-  switch (dsa_moe_w4_gemm_form(a.R)) {
+  switch (moe_host_form(a.R)) {
     case 1: return mw4_launch<1, GS>(a, E, st);
     case 2: return mw4_launch<2, GS>(a, E, st);
     case 4: return mw4_launch<4, GS>(a, E, st);
@@ -396,10 +385,7 @@ extern "C" hipError_t dsa_moe_w4_gemm(const void* X, long ldx, int xrows, int sr
                                       int E, int N, int K, int g, int S, hipStream_t st) {
   if (!dsa_moe_w4_gemm_supported(R, N, K, g) || k < 1 || k > MW4_MAXK || E < k || E > MW4_MAXE)
     return hipErrorInvalidValue;
-  if (S < 1 || K % (MW4_BK * MW4_UNROLL * S) || part == nullptr) return hipErrorInvalidValue;
-  if (ldx % 8 || ldx < K || src_div < 1 || xrows < 1 || (long)xrows * src_div < (long)R * k)
-    return hipErrorInvalidValue;
-  if (((long)(xrows - 1) * ldx + K) * 2 > 0xffffffffL) return hipErrorInvalidValue;  // X through a 32-bit buffer range
+  if (!mw4_slices(K, S) || part == nullptr || !moe_host_x_ok(ldx, xrows, src_div, R, k, K)) return hipErrorInvalidValue;
   MoeW4Args a{(const bf16_t*)X, (const uint8_t*)W, (const uint8_t*)Z, (const uint8_t*)SC, counts, lists, part, ldx,
               xrows, src_div, R, R * k, N, K, S};
   return g == 128 ? mw4_launch_form<1>(a, E, st) : g == 64 ? mw4_launch_form<2>(a, E, st) : mw4_launch_form<4>(a, E, st);

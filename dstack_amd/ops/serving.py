@@ -15,6 +15,7 @@ A token's cache slot is ``page * PAGE + offset``.
 from __future__ import annotations
 
 import math
+from typing import Callable, NamedTuple
 
 import torch
 
@@ -948,12 +949,18 @@ def moe_gemm(x: torch.Tensor, src_div: int, W: torch.Tensor, counts: torch.Tenso
     slice ``s`` of ``split``, fp32 [split, R k, N], for the pairs in ``lists`` (other rows of ``part``
     are not written).  ``x`` bf16 [R, K] with ``src_div = k`` (every pair of a row reads the row) or
     [R k, K] with ``src_div = 1``; ``W`` bf16 [E, N, K], N % 256 == 0, K % (512 split) == 0."""
-    P = x.shape[0] * src_div
+    return _moe_gemm("moe_gemm", x, src_div, (W,), W.shape[1], counts, lists, split, part, lambda: W)
+
+
+def _moe_gemm(binding, x, src_div, weight, N, counts, lists, split, part, ref_weight):
+    """What :func:`moe_gemm`, :func:`moe_fine_gemm` and :func:`moe_w4_gemm` do around their binding: without
+    the kernels :func:`moe_gemm_ref` over ``ref_weight()`` [E, N, K]; else ``part`` allocated where the caller
+    gave none and ``binding`` called with ``weight``, its arguments between ``src_div`` and ``counts``."""
     if not _ext.use_hip(x):
-        return moe_gemm_ref(x, src_div, W, counts, lists, split)
+        return moe_gemm_ref(x, src_div, ref_weight(), counts, lists, split)
     if part is None:
-        part = torch.empty(split, P, W.shape[1], dtype=torch.float32, device=x.device)
-    _ext.require().moe_gemm(x, src_div, W, counts, lists, part)
+        part = torch.empty(split, x.shape[0] * src_div, N, dtype=torch.float32, device=x.device)
+    getattr(_ext.require(), binding)(x, src_div, *weight, counts, lists, part)
     return part
 
 
@@ -1002,6 +1009,32 @@ def moe_combine(part: torch.Tensor, topk_w: torch.Tensor, live: torch.Tensor,
     return out
 
 
+class _MoeForm(NamedTuple):
+    """One routed expert GEMM as :class:`MoeWorkspace` and the MLP around it see it."""
+    supported: Callable  # (R, N, K) -> the kernel covers the shape
+    split: Callable  # (R, k, E, N, K) -> K slices
+    gemm: Callable  # (x, src_div, W, counts, lists, split, part=) -> part
+    max_experts: int
+    field: str  # how the family's config.json names the experts
+    shapes: str  # what the kernel asks of the hidden and FFN sizes, for the error that refuses them
+
+
+def _moe_form(w4_group: int | None, fine: bool) -> _MoeForm:
+    """bf16 experts (csrc/moe.hip), W4 experts of group size ``w4_group`` (csrc/moe_w4.hip) or many small
+    bf16 experts (``fine``: csrc/moe_fine.hip)."""
+    assert not (fine and w4_group is not None)
+    C = _ext.require()
+    if fine:
+        return _MoeForm(C.moe_fine_gemm_supported, C.moe_fine_gemm_split, moe_fine_gemm, MOE_FINE_MAX_EXPERTS, "num_experts",
+                        "multiples of 256 and at least 512 (the fine-grained expert GEMM's K-steps)")
+    tiles = "multiples of 512 (the grouped decode GEMM's tiles)"
+    if w4_group is None:
+        return _MoeForm(C.moe_gemm_supported, C.moe_gemm_split, moe_gemm, MOE_MAX_EXPERTS, "num_local_experts", tiles)
+    return _MoeForm(lambda R, N, K: C.moe_w4_gemm_supported(R, N, K, w4_group), C.moe_w4_gemm_split,
+                    lambda x, src_div, W, *routed, part: moe_w4_gemm(x, src_div, W, w4_group, *routed, part),
+                    MOE_MAX_EXPERTS, "num_local_experts", f"{tiles}, the AWQ group size {w4_group} one of 32, 64, 128")
+
+
 class MoeWorkspace:
     """The buffers of :func:`moe_mlp` for up to 256 rows of one model shape, allocated once (a captured
     graph holds their addresses): routing, the fp32 split-K partials of the larger of the two GEMMs
@@ -1012,26 +1045,13 @@ class MoeWorkspace:
         checked against ``moe_w4_gemm`` and the per-row split table comes from its rule.  ``fine``: the
         workspace of :func:`moe_fine_mlp` -- up to 128 experts, the shapes checked against ``moe_fine_gemm``
         and the splits from its rule."""
-        assert not (fine and w4_group is not None)
-        moe_check(E, k, MOE_FINE_MAX_EXPERTS if fine else MOE_MAX_EXPERTS, "num_experts" if fine else "num_local_experts")
-        C = _ext.require()
-        self.fine = fine
-        if fine:
-            ok, split = (lambda r, n, kk: C.moe_fine_gemm_supported(r, n, kk)), C.moe_fine_gemm_split
-        elif w4_group is None:
-            ok, split = (lambda r, n, kk: C.moe_gemm_supported(r, n, kk)), C.moe_gemm_split
-        else:
-            ok, split = (lambda r, n, kk: C.moe_w4_gemm_supported(r, n, kk, w4_group)), C.moe_w4_gemm_split
-        if fine and not (ok(MOE_MAX_ROWS, 2 * F, D) and ok(MOE_MAX_ROWS, D, F)):
-            raise ValueError(f"mixture of experts: hidden size {D} and FFN size {F} must be multiples of 256 and at "
-                             "least 512 (the fine-grained expert GEMM's K-steps)")
-        if not (ok(MOE_MAX_ROWS, 2 * F, D) and ok(MOE_MAX_ROWS, D, F)):
-            raise ValueError(f"mixture of experts: hidden size {D} and FFN size {F} must be multiples of 512 (the "
-                             "grouped decode GEMM's tiles)" + ("" if w4_group is None else
-                                                              f", the AWQ group size {w4_group} one of 32, 64, 128"))
-        self.E, self.k, self.D, self.F, self.w4_group = E, k, D, F, w4_group
+        form = self._form = _moe_form(w4_group, fine)
+        moe_check(E, k, form.max_experts, form.field)
         R = MOE_MAX_ROWS
-        self.split = {r: (split(r, k, E, 2 * F, D), split(r, k, E, D, F)) for r in range(1, R + 1)}
+        if not (form.supported(R, 2 * F, D) and form.supported(R, D, F)):
+            raise ValueError(f"mixture of experts: hidden size {D} and FFN size {F} must be {form.shapes}")
+        self.E, self.k, self.D, self.F, self.w4_group, self.fine = E, k, D, F, w4_group, fine
+        self.split = {r: (form.split(r, k, E, 2 * F, D), form.split(r, k, E, D, F)) for r in range(1, R + 1)}
         floats = max(max(s1 * r * k * 2 * F, s2 * r * k * D) for r, (s1, s2) in self.split.items())
         i32 = dict(dtype=torch.int32, device=device)
         self.topk_e, self.topk_w = torch.zeros(R * k, **i32), torch.zeros(R * k, dtype=torch.float32, device=device)
@@ -1048,6 +1068,14 @@ def moe_mlp(h: torch.Tensor, router: torch.Tensor, wgu: torch.Tensor, wdown: tor
     """The MoE MLP of up to 256 rows on the kernels: route, grouped gate/up GEMM over the layer input,
     reduce + SwiGLU, grouped down GEMM over the per-pair activations, reduce + weighted sum.  No host
     read, nothing allocated but the result: capturable.  ``ws``: :class:`MoeWorkspace`."""
+    assert not ws.fine and ws.w4_group is None
+    return _moe_mlp(h, router, wgu, wdown, k, live, ws)
+
+
+def _moe_mlp(h, router, wgu, wdown, k, live, ws):
+    """:func:`moe_mlp`, :func:`moe_fine_mlp` and :func:`moe_w4_mlp`: the expert GEMM is the one of the
+    workspace's form, the weights what that GEMM takes."""
+    gemm = ws._form.gemm
     R, E, D, F = h.shape[0], router.shape[0], ws.D, ws.F
     if h.stride(-1) != 1 or h.stride(0) % 8 or h.data_ptr() % 16:
         h = h.contiguous()
@@ -1055,9 +1083,9 @@ def moe_mlp(h: torch.Tensor, router: torch.Tensor, wgu: torch.Tensor, wdown: tor
     P = R * k
     topk_e, topk_w, counts, lists = moe_route(
         h, router, live, k, out=(ws.topk_e[:P].view(R, k), ws.topk_w[:P].view(R, k), ws.counts, ws.lists[: E * R].view(E, R)))
-    part = moe_gemm(h, k, wgu, counts, lists, s1, part=ws.part[: s1 * P * 2 * F].view(s1, P, 2 * F))
+    part = gemm(h, k, wgu, counts, lists, s1, part=ws.part[: s1 * P * 2 * F].view(s1, P, 2 * F))
     a = moe_swiglu(part, live, out=ws.a[:P])
-    part = moe_gemm(a, 1, wdown, counts, lists, s2, part=ws.part[: s2 * P * D].view(s2, P, D))
+    part = gemm(a, 1, wdown, counts, lists, s2, part=ws.part[: s2 * P * D].view(s2, P, D))
     return moe_combine(part, topk_w, live)
 
 
@@ -1107,12 +1135,7 @@ def moe_fine_gemm(x: torch.Tensor, src_div: int, W: torch.Tensor, counts: torch.
     """:func:`moe_gemm` on the kernel for many small experts: up to 128 experts, ``W`` bf16 [E, N, K] with
     N % 128 == 0 and every K slice (K / split) a multiple of 256 and at least 512; an expert with more
     than 64 pairs is worked in passes.  Without the kernels: :func:`moe_gemm_ref`."""
-    if not _ext.use_hip(x):
-        return moe_gemm_ref(x, src_div, W, counts, lists, split)
-    if part is None:
-        part = torch.empty(split, x.shape[0] * src_div, W.shape[1], dtype=torch.float32, device=x.device)
-    _ext.require().moe_fine_gemm(x, src_div, W, counts, lists, part)
-    return part
+    return _moe_gemm("moe_fine_gemm", x, src_div, (W,), W.shape[1], counts, lists, split, part, lambda: W)
 
 
 def moe_fine_mlp(h: torch.Tensor, router: torch.Tensor, wgu: torch.Tensor, wdown: torch.Tensor, k: int,
@@ -1120,17 +1143,7 @@ def moe_fine_mlp(h: torch.Tensor, router: torch.Tensor, wgu: torch.Tensor, wdown
     """:func:`moe_mlp` of up to 256 rows with :func:`moe_fine_gemm` between the same router, SwiGLU and
     combine kernels.  Capturable.  ``ws``: a :class:`MoeWorkspace` made with ``fine=True``."""
     assert ws.fine
-    R, E, D, F = h.shape[0], router.shape[0], ws.D, ws.F
-    if h.stride(-1) != 1 or h.stride(0) % 8 or h.data_ptr() % 16:
-        h = h.contiguous()
-    s1, s2 = ws.split[R]
-    P = R * k
-    topk_e, topk_w, counts, lists = moe_route(
-        h, router, live, k, out=(ws.topk_e[:P].view(R, k), ws.topk_w[:P].view(R, k), ws.counts, ws.lists[: E * R].view(E, R)))
-    part = moe_fine_gemm(h, k, wgu, counts, lists, s1, part=ws.part[: s1 * P * 2 * F].view(s1, P, 2 * F))
-    a = moe_swiglu(part, live, out=ws.a[:P])
-    part = moe_fine_gemm(a, 1, wdown, counts, lists, s2, part=ws.part[: s2 * P * D].view(s2, P, D))
-    return moe_combine(part, topk_w, live)
+    return _moe_mlp(h, router, wgu, wdown, k, live, ws)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1156,13 +1169,9 @@ def moe_w4_gemm(x: torch.Tensor, src_div: int, W, g: int, counts: torch.Tensor, 
     x[p // src_div] @ ((q - z) * s)[expert(p)]^T`` over K slice ``s``, fp32 [split, R k, N].  N % 256 == 0,
     K % (512 split) == 0.  Without the kernels: the experts dequantized to fp32, then :func:`moe_gemm_ref`."""
     codes, zeros, scales = W
-    if not _ext.use_hip(x):
-        return moe_gemm_ref(x, src_div, moe_w4_dequant_ref(W, g), counts, lists, split)
     N, K = codes.shape[1], 2 * codes.shape[2]
-    if part is None:
-        part = torch.empty(split, x.shape[0] * src_div, N, dtype=torch.float32, device=x.device)
-    _ext.require().moe_w4_gemm(x, src_div, codes, zeros, scales, N, K, g, counts, lists, part)
-    return part
+    return _moe_gemm("moe_w4_gemm", x, src_div, (codes, zeros, scales, N, K, g), N, counts, lists, split, part,
+                     lambda: moe_w4_dequant_ref(W, g))
 
 
 def moe_w4_mlp(h: torch.Tensor, router: torch.Tensor, wgu, wdown, g: int, k: int, live: torch.Tensor,
@@ -1171,17 +1180,7 @@ def moe_w4_mlp(h: torch.Tensor, router: torch.Tensor, wgu, wdown, g: int, k: int
     group size ``g``): route, W4 gate/up GEMM, reduce + SwiGLU, W4 down GEMM, reduce + weighted sum.
     Capturable.  ``ws``: a :class:`MoeWorkspace` made with ``w4_group=g``."""
     assert ws.w4_group == g, (ws.w4_group, g)
-    R, E, D, F = h.shape[0], router.shape[0], ws.D, ws.F
-    if h.stride(-1) != 1 or h.stride(0) % 8 or h.data_ptr() % 16:
-        h = h.contiguous()
-    s1, s2 = ws.split[R]
-    P = R * k
-    topk_e, topk_w, counts, lists = moe_route(
-        h, router, live, k, out=(ws.topk_e[:P].view(R, k), ws.topk_w[:P].view(R, k), ws.counts, ws.lists[: E * R].view(E, R)))
-    part = moe_w4_gemm(h, k, wgu, g, counts, lists, s1, part=ws.part[: s1 * P * 2 * F].view(s1, P, 2 * F))
-    a = moe_swiglu(part, live, out=ws.a[:P])
-    part = moe_w4_gemm(a, 1, wdown, g, counts, lists, s2, part=ws.part[: s2 * P * D].view(s2, P, D))
-    return moe_combine(part, topk_w, live)
+    return _moe_mlp(h, router, wgu, wdown, k, live, ws)
 
 
 def moe_w4_mlp_eager(h: torch.Tensor, router: torch.Tensor, wgu, wdown, g: int, k: int, live: torch.Tensor | None,

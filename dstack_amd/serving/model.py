@@ -450,6 +450,17 @@ class ServingLlama:
         self.moe_fine = bool(self.E) and spec.family == "qwen3_moe"
         self.moe_ws = sops.MoeWorkspace(self.E, self.topk, cfg.dim, cfg.ffn_dim, self.device, w4_group=self.moe_w4_group,
                                         fine=self.moe_fine) if self.E and self.hip else None
+        # how the GPU runs (h, router, wgu, wdown, live), by whether the layer's experts are ``Awq4Experts``: up to 256
+        # rows on the kernels, more rows eagerly (with the W4 scratch).  The closures hold no reference to the model:
+        # it is freed when its last user lets go of it, not at a later collection
+        k, ws, mlp = self.topk, self.moe_ws, sops.moe_fine_mlp if self.moe_fine else sops.moe_mlp
+        self._moe_run = {
+            False: (lambda h, r, u, d, live: mlp(h, r, u, d, k, live, ws),
+                    lambda h, r, u, d, live, scratch: sops.moe_mlp_eager(h, r, u, d, k, live)),
+            True: (lambda h, r, u, d, live: sops.moe_w4_mlp(h, r, u.stored, d.stored, u.g, k, live, ws),
+                   lambda h, r, u, d, live, scratch: sops.moe_w4_mlp_eager(h, r, u.stored, d.stored, u.g, k, live, scratch)),
+        }
+        self._w4_scratch = None  # (_alloc_w4_scratch, once the W4 weights are known)
         self._moe_live = None  # int32 [rows] of the running step: > 0 where the row holds a token
         # DSTACK_AMD_GEMV=0: small decode batches on hipBLASLt too (A/B switch)
         self.gemv = os.environ.get("DSTACK_AMD_GEMV", "1") != "0"
@@ -1275,39 +1286,26 @@ class ServingLlama:
 
     def _moe_mlp(self, L, h):
         """The experts' MLP of ``h`` [rows, dim]; ``self._moe_live`` says which rows hold a token (the
-        others come out as zeros).  GPU: up to 256 rows (a decode batch, a verify step, a short
-        prefill) on the kernels of ``csrc/moe.hip`` -- no host read, so the step can be captured; more
-        rows (prefill) on one library GEMM pair per non-empty expert (``sops.moe_mlp_eager``), which
-        reads the routing counts on the host once per layer.  CPU: ``ref.moe_mlp`` for every row
-        count.  All three read the same ``wgu`` [E, 2F, D] and ``wdown`` [E, D, F].
-
-        AWQ experts (``Awq4Experts``): up to 256 rows on the W4 grouped GEMM of ``csrc/moe_w4.hip``
-        between the same router, SwiGLU and combine kernels (``sops.moe_w4_mlp``); more rows dequantize
-        one expert at a time into the W4 scratch for the library GEMM pair (``sops.moe_w4_mlp_eager``);
-        CPU: ``ref.moe_mlp`` on the experts dequantized to fp32.
-
-        qwen3_moe (``self.moe_fine``): ``sops.moe_fine_mlp`` (``csrc/moe_fine.hip``) for every row count, a
-        prefill in chunks of 256 rows with ``live`` sliced alongside -- no host read on any path."""
-        if isinstance(L["wgu"], Awq4Experts):
-            wgu, wdown = L["wgu"], L["wdown"]
-            if not self.hip:
-                return ref.moe_mlp(h, L["router"], wgu.dequantized().to(h.dtype), wdown.dequantized().to(h.dtype),
-                                   self.topk, self._moe_live)
-            if h.shape[0] <= sops.MOE_MAX_ROWS:
-                return sops.moe_w4_mlp(h, L["router"], wgu.stored, wdown.stored, wgu.g, self.topk, self._moe_live,
-                                       self.moe_ws)
-            return sops.moe_w4_mlp_eager(h, L["router"], wgu.stored, wdown.stored, wgu.g, self.topk, self._moe_live,
-                                         self._w4_scratch)
+        others come out as zeros).  CPU: ``ref.moe_mlp``, AWQ experts dequantized to fp32 first.  GPU:
+        up to 256 rows (a decode batch, a verify step, a short prefill) on the kernels of the experts'
+        form (``sops.moe_mlp``, ``moe_w4_mlp`` or ``moe_fine_mlp``) -- no host read, so the step can be
+        captured.  More rows (prefill): qwen3_moe in chunks of 256 rows on the same kernels, ``live``
+        sliced alongside; the others on one library GEMM pair per non-empty expert
+        (``sops.moe_mlp_eager``; ``moe_w4_mlp_eager`` dequantizes one expert at a time into the W4
+        scratch), which reads the routing counts on the host once per layer."""
+        router, wgu, wdown, live = L["router"], L["wgu"], L["wdown"], self._moe_live
+        w4 = isinstance(wgu, Awq4Experts)
         if not self.hip:
-            return ref.moe_mlp(h, L["router"], L["wgu"], L["wdown"], self.topk, self._moe_live)
-        if self.moe_fine:  # every row count on the kernels, 256 rows at a time through the one workspace
-            n = sops.MOE_MAX_ROWS
-            ys = [sops.moe_fine_mlp(h[i : i + n], L["router"], L["wgu"], L["wdown"], self.topk, self._moe_live[i : i + n],
-                                    self.moe_ws) for i in range(0, h.shape[0], n)]
-            return ys[0] if len(ys) == 1 else torch.cat(ys)
-        if h.shape[0] <= sops.MOE_MAX_ROWS:
-            return sops.moe_mlp(h, L["router"], L["wgu"], L["wdown"], self.topk, self._moe_live, self.moe_ws)
-        return sops.moe_mlp_eager(h, L["router"], L["wgu"], L["wdown"], self.topk, self._moe_live)
+            if w4:
+                wgu, wdown = wgu.dequantized().to(h.dtype), wdown.dequantized().to(h.dtype)
+            return ref.moe_mlp(h, router, wgu, wdown, self.topk, live)
+        kernels, eager = self._moe_run[w4]
+        n = sops.MOE_MAX_ROWS
+        if h.shape[0] <= n:
+            return kernels(h, router, wgu, wdown, live)
+        if self.moe_fine:  # through the one workspace
+            return torch.cat([kernels(h[i : i + n], router, wgu, wdown, live[i : i + n]) for i in range(0, h.shape[0], n)])
+        return eager(h, router, wgu, wdown, live, self._w4_scratch)
 
     @staticmethod
     def _rows(h) -> int:

@@ -240,6 +240,76 @@ def test_gpu_mlp_no_worse_than_library_path(gpu, R, capsys):
     assert err <= err_eager
 
 
+ROWS = (1, 16, 17, 64, 128, 256)
+SHAPES = {"mixtral-8x7b": (8, 2, 4096, 14336), "mixtral-8x22b": (8, 2, 6144, 16384),
+          "qwen3-30b-a3b": (128, 8, 2048, 768)}  # experts, per token, hidden, FFN
+# (rule, model) -> K slices of the gate/up GEMM and of the down GEMM at ROWS, recorded from the build of the commit
+# before the three rules were merged into one (128 experts are past the limit of the first two: 0)
+SPLITS = {
+    ("moe_gemm_split", "mixtral-8x7b"): ([2, 1, 1, 1, 1, 1], [14, 4, 4, 4, 4, 4]),
+    ("moe_gemm_split", "mixtral-8x22b"): ([2, 1, 1, 1, 1, 1], [8, 2, 2, 2, 2, 2]),
+    ("moe_gemm_split", "qwen3-30b-a3b"): ([0, 0, 0, 0, 0, 0], [0, 0, 0, 0, 0, 0]),
+    ("moe_w4_gemm_split", "mixtral-8x7b"): ([2, 1, 1, 1, 1, 1], [14, 4, 4, 4, 4, 2]),
+    ("moe_w4_gemm_split", "mixtral-8x22b"): ([2, 1, 1, 1, 1, 1], [8, 2, 2, 2, 2, 2]),
+    ("moe_w4_gemm_split", "qwen3-30b-a3b"): ([0, 0, 0, 0, 0, 0], [0, 0, 0, 0, 0, 0]),
+    ("moe_fine_gemm_split", "mixtral-8x7b"): ([1, 1, 1, 1, 1, 1], [8, 2, 2, 2, 2, 2]),
+    ("moe_fine_gemm_split", "mixtral-8x22b"): ([1, 1, 1, 1, 1, 1], [4, 1, 1, 1, 1, 1]),
+    ("moe_fine_gemm_split", "qwen3-30b-a3b"): ([4, 1, 1, 1, 1, 1], [1, 1, 1, 1, 1, 1]),
+}
+
+
+@pytest.mark.gpu
+def test_gpu_split_rules_give_the_recorded_slices(gpu):
+    """The K slices decide speed only (every exact-GEMM test passes at any of them), so the three rules are held
+    to what they gave at the served models' shapes; a shape a kernel does not run gives 0 (K % 512, N % 256,
+    K < 512)."""
+    for (rule, model), want in SPLITS.items():
+        E, k, D, F = SHAPES[model]
+        got = ([getattr(sops, rule)(R, k, E, 2 * F, D) for R in ROWS], [getattr(sops, rule)(R, k, E, D, F) for R in ROWS])
+        assert got == want, (rule, model)
+    assert sops.moe_gemm_split(16, 2, 8, 512, 768) == 0 and sops.moe_w4_gemm_split(16, 2, 8, 384, 1024) == 0
+    assert sops.moe_fine_gemm_split(16, 8, 128, 512, 384) == 0
+
+
+def _mlp_equals_its_steps(gpu, mlp, gemm, workspace, router, wgu, wdown, k, D=512):
+    """``mlp(h, router, wgu, wdown, k, live, ws)`` returns the bits of the five public calls it stands for --
+    ``moe_route``, ``gemm(x, src_div, W, counts, lists, split)`` with the workspace's split, ``moe_swiglu``, ``gemm``,
+    ``moe_combine`` -- composed here on freshly allocated buffers: for one row; for 17 rows (a second, partly
+    filled token block) of which row 5 is dead; for the same rows as a column slice whose row stride is no
+    multiple of 16 bytes, which the MLP has to copy; and for one row through a workspace that 17 rows went
+    through before, none of whose stale rows may be read."""
+    wide = torch.randn(17, D + 4, generator=torch.Generator().manual_seed(k)).to(gpu, torch.bfloat16)
+    live = torch.ones(17, dtype=torch.int32, device=gpu)
+    live[5] = 0
+
+    def steps(h, live):
+        topk_e, topk_w, counts, lists = sops.moe_route(h, router, live, k)
+        s1, s2 = workspace().split[h.shape[0]]
+        a = sops.moe_swiglu(gemm(h, k, wgu, counts, lists, s1), live)
+        return sops.moe_combine(gemm(a, 1, wdown, counts, lists, s2), topk_w, live)
+
+    h17 = wide[:, :D].contiguous()
+    h1 = h17[:1]
+    want17, want1 = steps(h17, live), steps(h1, live[:1])
+    assert want17[4].any() and not want17[5].any() and want1.any()
+    assert not wide[:, :D].is_contiguous() and wide.stride(0) % 8
+    assert torch.equal(mlp(h1, router, wgu, wdown, k, live[:1], workspace()), want1)
+    ws = workspace()
+    assert torch.equal(mlp(h17, router, wgu, wdown, k, live, workspace()), want17)
+    assert torch.equal(mlp(wide[:, :D], router, wgu, wdown, k, live, ws), want17)
+    assert torch.equal(mlp(h1, router, wgu, wdown, k, live[:1], ws), want1)
+
+
+@pytest.mark.gpu
+def test_gpu_mlp_equals_its_steps(gpu):
+    g = torch.Generator().manual_seed(0)
+    E, k, D, F = 8, 2, 512, 512
+    router = torch.randn(E, D, generator=g).to(gpu, torch.bfloat16)
+    wgu = (torch.randn(E, 2 * F, D, generator=g) / D ** 0.5).to(gpu, torch.bfloat16)
+    wdown = (torch.randn(E, D, F, generator=g) / F ** 0.5).to(gpu, torch.bfloat16)
+    _mlp_equals_its_steps(gpu, sops.moe_mlp, sops.moe_gemm, lambda: sops.MoeWorkspace(E, k, D, F, gpu), router, wgu, wdown, k)
+
+
 GPU_KW = dict(device="cuda", max_model_len=512, max_batch=8, num_pages=64)
 PROMPTS = [[1, 2, 3, 4, 5, 1, 2, 3, 4, 5, 1, 2, 3], list(range(7, 90))]
 

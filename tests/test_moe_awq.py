@@ -13,7 +13,7 @@ from dstack_amd.ops import serving as sops
 from dstack_amd.serving.engine import LLMEngine, SamplingParams
 from dstack_amd.serving.model import Awq4Experts, Awq4Weight
 from tests.test_awq import _exact_case, pack_awq
-from tests.test_moe import GPU_KW, PROMPTS, _mlp64, _patterns, _tiny_mixtral
+from tests.test_moe import GPU_KW, PROMPTS, _mlp64, _mlp_equals_its_steps, _patterns, _tiny_mixtral
 
 
 def _experts(gpu, E, M, N, K, g, seed, long_k=False):
@@ -94,6 +94,19 @@ def test_gpu_mlp_no_worse_than_the_bf16_kernels(gpu, R, capsys):
         print(f"\nmoe_w4_mlp R={R}: rms error W4 kernels {err:.3e}, bf16 kernels on bf16((q - z) s) {err_bf16:.3e}, rms of "
               f"the result {want.pow(2).mean().sqrt().item():.3e}")
     assert err <= err_bf16
+
+
+@pytest.mark.gpu
+def test_gpu_mlp_equals_its_steps(gpu):
+    gen = torch.Generator().manual_seed(0)
+    E, k, D, F, g = 8, 2, 512, 512, 128
+    router = torch.randn(E, D, generator=gen).to(gpu, torch.bfloat16)
+    wgu, wdown = (tuple(torch.stack(t).to(gpu) for t in zip(*(
+        sops.w4_shuffle(*ref.quant_w4(torch.randn(N, K, generator=gen) / K ** 0.5, g), g) for _ in range(E))))
+        for N, K in ((2 * F, D), (D, F)))
+    _mlp_equals_its_steps(gpu, lambda h, r, u, d, *a: sops.moe_w4_mlp(h, r, u, d, g, *a),
+                          lambda x, src_div, W, *a: sops.moe_w4_gemm(x, src_div, W, g, *a),
+                          lambda: sops.MoeWorkspace(E, k, D, F, gpu, w4_group=g), router, wgu, wdown, k)
 
 
 # ---------------------------------------------------------------------------------------------

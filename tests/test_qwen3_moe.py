@@ -11,7 +11,7 @@ import torch
 from dstack_amd.ops import reference as ref
 from dstack_amd.ops import serving as sops
 from dstack_amd.serving.engine import LLMEngine, SamplingParams
-from tests.test_moe import _mlp64, _patterns
+from tests.test_moe import _mlp64, _mlp_equals_its_steps, _patterns
 
 
 def _tiny_qwen3_moe(root, hidden, ffn, experts, per_tok):
@@ -196,6 +196,18 @@ def test_gpu_fine_mlp_no_worse_than_library_path(gpu, R, capsys):
         print(f"\nmoe_fine_mlp R={R}: rms error kernels {err:.3e}, eager library path {err_eager:.3e}, rms of the "
               f"result {want.pow(2).mean().sqrt().item():.3e}")
     assert err <= err_eager
+
+
+@pytest.mark.gpu
+def test_gpu_fine_mlp_equals_its_steps(gpu):
+    """72 experts: past 64, so the router's two-per-lane form runs."""
+    g = torch.Generator().manual_seed(0)
+    E, k, D, F = 72, 8, 512, 512
+    router = torch.randn(E, D, generator=g).to(gpu, torch.bfloat16)
+    wgu = (torch.randn(E, 2 * F, D, generator=g) / D ** 0.5).to(gpu, torch.bfloat16)
+    wdown = (torch.randn(E, D, F, generator=g) / F ** 0.5).to(gpu, torch.bfloat16)
+    _mlp_equals_its_steps(gpu, sops.moe_fine_mlp, sops.moe_fine_gemm, lambda: sops.MoeWorkspace(E, k, D, F, gpu, fine=True),
+                          router, wgu, wdown, k)
 
 
 GPU_KW = dict(device="cuda", max_model_len=512, max_batch=8, num_pages=64)

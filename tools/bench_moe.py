@@ -43,6 +43,18 @@ def timed(fn, iters):
     return s.elapsed_time(e) / iters * 1e3  # us
 
 
+def measure(paths, reps, iters):
+    """Every path warmed up (code objects, library algorithm choice), then the paths alternating, ``reps`` times:
+    name -> the us per call of each repetition, name -> their median."""
+    for fn in paths.values():
+        timed(fn, 8)
+    t = {name: [] for name in paths}
+    for _ in range(reps):
+        for name, fn in paths.items():
+            t[name].append(timed(fn, iters))
+    return t, {name: statistics.median(v) for name, v in t.items()}
+
+
 def w4_table(dev, draw, router, wgu, wdown, ws, rows, reps, iters, g=128):
     from dstack_amd.ops import reference as ref
 
@@ -74,13 +86,7 @@ def w4_table(dev, draw, router, wgu, wdown, ws, rows, reps, iters, g=128):
             "mlp": lambda i: sops.moe_mlp(hs[i % 8], router, wgu, wdown, TOPK, live, ws),
             "mlp4": lambda i: sops.moe_w4_mlp(hs[i % 8], router, qgu, qdown, g, TOPK, live, ws4),
         }
-        for fn in paths.values():
-            timed(fn, 8)
-        t = {name: [] for name in paths}
-        for _ in range(reps):
-            for name, fn in paths.items():
-                t[name].append(timed(fn, iters))
-        med = {name: statistics.median(v) for name, v in t.items()}
+        t, med = measure(paths, reps, iters)
         cell = {name: f"{med[name]:8.1f} ({min(v):.0f}..{max(v):.0f})" for name, v in t.items()}
         lines.append(f"{R:6d} {sops._ext.require().moe_w4_gemm_form(R):4d} | {b1},{b2} {s1},{s2} | "
                      + " | ".join(f"{cell[a]} {cell[a + '4']} {med[a] / med[a + '4']:.2f}x" for a in ("gu", "dn", "mlp")))
@@ -126,13 +132,7 @@ def fine_table(dev, draw, shape, rows, reps, iters):
             paths["gu0"] = lambda i: sops.moe_gemm(hs[i % 8], TOPK, wgu, *routed[i % 8][2:], b1, part=part(old, b1, 2 * F))
             paths["dn0"] = lambda i: sops.moe_gemm(acts[i % 8], 1, wdown, *routed[i % 8][2:], b2, part=part(old, b2, D))
             paths["mlp0"] = lambda i: sops.moe_mlp(hs[i % 8], router, wgu, wdown, TOPK, live, old)
-        for fn in paths.values():
-            timed(fn, 8)
-        t = {name: [] for name in paths}
-        for _ in range(reps):
-            for name, fn in paths.items():
-                t[name].append(timed(fn, iters))
-        med = {name: statistics.median(v) for name, v in t.items()}
+        t, med = measure(paths, reps, iters)
         cell = {name: f"{med[name]:7.1f} ({min(v):.0f}..{max(v):.0f})" for name, v in t.items()}
         gbs = {"gu": chosen * 2 * F * D * 2 / med["gu"] / 1e3, "dn": chosen * F * D * 2 / med["dn"] / 1e3}
         lines.append(f"{R:6d} {s1},{s2} {chosen:6.1f} | "
@@ -189,13 +189,7 @@ def main():
             "kernels": lambda i: sops.moe_mlp(hs[i % 8], router, wgu, wdown, TOPK, live, ws),
             "eager": lambda i: sops.moe_mlp_eager(hs[i % 8], router, wgu, wdown, TOPK, live),
         }
-        for fn in paths.values():  # warm-up: code objects, library algorithm choice
-            timed(fn, 8)
-        t = {name: [] for name in paths}
-        for _ in range(reps):
-            for name, fn in paths.items():
-                t[name].append(timed(fn, iters))
-        med = {name: statistics.median(v) for name, v in t.items()}
+        t, med = measure(paths, reps, iters)
         sp = {name: f"({min(v):.0f}..{max(v):.0f})" for name, v in t.items()}
         gbs = chosen * 2 * F * D * 2 / med["gemm"] / 1e3
         lines.append(f"{R:6d} {sops._ext.require().moe_gemm_form(R):4d} {s1:5d},{s2:<5d} {chosen:12.1f} | "
