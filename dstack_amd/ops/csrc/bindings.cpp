@@ -133,6 +133,11 @@ bool dsa_moe_w4_gemm_supported(int, int, int, int);
 int dsa_moe_w4_gemm_split(int, int, int, int, int);
 hipError_t dsa_moe_w4_gemm(const void*, long, int, int, const void*, const void*, const void*, const int*, const int*,
                            float*, int, int, int, int, int, int, int, hipStream_t);
+int dsa_moe_prefill_tiles(int, int, int, int);
+bool dsa_moe_prefill_gemm_supported(int, int);
+hipError_t dsa_moe_prefill_plan(const int*, const int*, int*, int*, int, int, int, int, hipStream_t);
+hipError_t dsa_moe_prefill_gemm(const void*, long, int, int, const void*, const int*, const int*, float*, void*, int, int,
+                                int, int, int, int, hipStream_t);
 hipError_t dsa_moe_lists(const int*, const int*, int*, int*, int, int, int, hipStream_t);
 hipError_t dsa_moe_route(const void*, long, const void*, const int*, int*, float*, int*, int*, int, int, int, int,
                          hipStream_t);
@@ -845,9 +850,10 @@ void check_moe_rows(const torch::Tensor& x, int64_t cols, const char* what, cons
 
 // max_e: 64 for the grouped GEMMs of csrc/moe.hip and csrc/moe_w4.hip, 128 for the router, the lists and
 // csrc/moe_fine.hip
-void check_moe_dims(int64_t R, int64_t k, int64_t E, const char* what, int64_t max_e = 64) {
-  TORCH_CHECK(R >= 1 && R <= 256 && k >= 1 && k <= 8 && E >= k && E <= max_e, what,
-              ": 1 <= rows <= 256, 1 <= experts per token <= 8, experts per token <= experts <= ", max_e);
+// max_r: 256 for the decode kernels, 2048 for csrc/moe_prefill.hip and for moe_swiglu / moe_combine, which follow both
+void check_moe_dims(int64_t R, int64_t k, int64_t E, const char* what, int64_t max_e = 64, int64_t max_r = 256) {
+  TORCH_CHECK(R >= 1 && R <= max_r && k >= 1 && k <= 8 && E >= k && E <= max_e, what, ": 1 <= rows <= ", max_r,
+              ", 1 <= experts per token <= 8, experts per token <= experts <= ", max_e);
 }
 
 bool moe_gemm_supported(int64_t R, int64_t N, int64_t K) {
@@ -976,7 +982,7 @@ void moe_swiglu(torch::Tensor part, torch::Tensor live, torch::Tensor a) {
   TORCH_CHECK(part.dim() == 3 && live.dim() == 1 && part.size(1) % live.size(0) == 0 && part.size(2) % 8 == 0,
               "moe_swiglu: part [S, R k, 2F], live [R]");
   const int64_t S = part.size(0), P = part.size(1), F = part.size(2) / 2, R = live.size(0);
-  check_moe_dims(R, P / R, P / R, "moe_swiglu");
+  check_moe_dims(R, P / R, P / R, "moe_swiglu", 64, 2048);
   check_moe(part, torch::kFloat32, {S, P, 2 * F}, "moe_swiglu part");
   check_moe(live, torch::kInt32, {R}, "moe_swiglu live");
   check_moe(a, torch::kBFloat16, {P, F}, "moe_swiglu a");
@@ -989,7 +995,7 @@ void moe_swiglu(torch::Tensor part, torch::Tensor live, torch::Tensor a) {
 void moe_combine(torch::Tensor part, torch::Tensor topk_w, torch::Tensor live, torch::Tensor y) {
   TORCH_CHECK(part.dim() == 3 && topk_w.dim() == 2 && part.size(2) % 4 == 0, "moe_combine: part [S, R k, N], topk_w [R, k]");
   const int64_t S = part.size(0), P = part.size(1), N = part.size(2), R = topk_w.size(0), k = topk_w.size(1);
-  check_moe_dims(R, k, k, "moe_combine");
+  check_moe_dims(R, k, k, "moe_combine", 64, 2048);
   check_moe(part, torch::kFloat32, {S, R * k, N}, "moe_combine part");
   check_moe(topk_w, torch::kFloat32, {R, k}, "moe_combine topk_w");
   check_moe(live, torch::kInt32, {R}, "moe_combine live");
@@ -997,6 +1003,57 @@ void moe_combine(torch::Tensor part, torch::Tensor topk_w, torch::Tensor live, t
   check(dsa_moe_combine(part.data_ptr<float>(), topk_w.data_ptr<float>(), live.data_ptr<int>(), y.data_ptr(), N, (int)R,
                         (int)k, (int)N, (int)S, stream()),
         "moe_combine");
+}
+
+// ---- routed expert GEMM of a prefill of up to 2048 rows (csrc/moe_prefill.hip) ----
+// the plan's two tensors for R rows, k per token, E experts: tile_e int32 [tiles], pairs int32 [tiles, tile]
+int64_t check_moe_prefill_plan(const char* op, int64_t R, int64_t k, int64_t E, const torch::Tensor& tile_e,
+                               const torch::Tensor& pairs) {
+  check_moe_dims(R, k, E, op, 128, 2048);
+  TORCH_CHECK(pairs.dim() == 2 && (pairs.size(1) == 64 || pairs.size(1) == 128), op, ": pairs [tiles, 64 or 128]");
+  const int64_t tile = pairs.size(1), tiles = dsa_moe_prefill_tiles((int)R, (int)k, (int)E, (int)tile);
+  check_moe(tile_e, torch::kInt32, {tiles}, op, " tile_e");
+  check_moe(pairs, torch::kInt32, {tiles, tile}, op, " pairs");
+  return tile;
+}
+
+// tile_e, pairs (the live pairs row k + j grouped by expert into tiles, -1 for padding) from topk_e [R, k], live [R]
+void moe_prefill_plan(torch::Tensor topk_e, torch::Tensor live, int64_t E, torch::Tensor tile_e, torch::Tensor pairs) {
+  TORCH_CHECK(topk_e.dim() == 2, "moe_prefill_plan: topk_e [R, k]");
+  const int64_t R = topk_e.size(0), k = topk_e.size(1);
+  const int64_t tile = check_moe_prefill_plan("moe_prefill_plan", R, k, E, tile_e, pairs);
+  check_moe(topk_e, torch::kInt32, {R, k}, "moe_prefill_plan topk_e");
+  check_moe(live, torch::kInt32, {R}, "moe_prefill_plan live");
+  check(dsa_moe_prefill_plan(topk_e.data_ptr<int>(), live.data_ptr<int>(), tile_e.data_ptr<int>(), pairs.data_ptr<int>(),
+                             (int)R, (int)k, (int)E, (int)tile, stream()),
+        "moe_prefill_plan");
+}
+
+// For the plan's pairs p: out fp32 [1, R k, N]: out[0][p] = x[p / src_div] W[expert(p)]^T (what moe_gemm writes with
+// one K slice); out bf16 [R k, N / 2]: out[p] = bf16(silu(g) u) of that product's halves.  x bf16 [R k / src_div, K],
+// W bf16 [E, N, K], N % 128 == 0, K % 64 == 0, K >= 128.
+void moe_prefill_gemm(torch::Tensor x, int64_t src_div, torch::Tensor W, torch::Tensor tile_e, torch::Tensor pairs,
+                      int64_t k, torch::Tensor out) {
+  TORCH_CHECK(x.dim() == 2 && W.dim() == 3 && k >= 1, "moe_prefill_gemm: x [rows, K], W [E, N, K]");
+  const int64_t E = W.size(0), N = W.size(1), K = W.size(2);
+  const bool glu = out.scalar_type() == torch::kBFloat16;
+  TORCH_CHECK(out.dim() == (glu ? 2 : 3) && out.size(glu ? 0 : 1) % k == 0, "moe_prefill_gemm: out fp32 [1, R k, N] or bf16 [R k, N / 2]");
+  const int64_t P = out.size(glu ? 0 : 1), R = P / k;
+  const int64_t tile = check_moe_prefill_plan("moe_prefill_gemm", R, k, E, tile_e, pairs);
+  TORCH_CHECK((src_div == 1 || src_div == k) && x.size(0) * src_div == P,
+              "moe_prefill_gemm: x has a row per pair (src_div 1) or per token row (src_div k)");
+  TORCH_CHECK(N <= INT_MAX && K <= INT_MAX && dsa_moe_prefill_gemm_supported((int)N, (int)K),
+              "moe_prefill_gemm: N % 128 == 0, K % 64 == 0, K >= 128");
+  check_moe_rows(x, K, "moe_prefill_gemm x");
+  check_moe(W, torch::kBFloat16, {E, N, K}, "moe_prefill_gemm W");
+  if (glu)
+    check_moe(out, torch::kBFloat16, {P, N / 2}, "moe_prefill_gemm a");
+  else
+    check_moe(out, torch::kFloat32, {1, P, N}, "moe_prefill_gemm part");
+  check(dsa_moe_prefill_gemm(x.data_ptr(), x.stride(0), (int)x.size(0), (int)src_div, W.data_ptr(), tile_e.data_ptr<int>(),
+                             pairs.data_ptr<int>(), glu ? nullptr : out.data_ptr<float>(), glu ? out.data_ptr() : nullptr,
+                             (int)R, (int)k, (int)E, (int)N, (int)K, (int)tile, stream()),
+        "moe_prefill_gemm");
 }
 
 // out[M][N] (+)= a[K][M]^T b[K][N]  (csrc/gemm_nt.hip KM form: dW = dY^T X, token-major operands);
@@ -1625,6 +1682,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return dsa_moe_fine_gemm_split((int)R, (int)k, (int)E, (int)N, (int)K);
         },
         "K slices moe_fine_gemm runs a shape with (0: unsupported)");
+  m.def("moe_prefill_plan", &moe_prefill_plan, pybind11::arg("topk_e"), pybind11::arg("live"), pybind11::arg("E"),
+        pybind11::arg("tile_e"), pybind11::arg("pairs"));
+  m.def("moe_prefill_gemm", &moe_prefill_gemm, pybind11::arg("x"), pybind11::arg("src_div"), pybind11::arg("W"),
+        pybind11::arg("tile_e"), pybind11::arg("pairs"), pybind11::arg("k"), pybind11::arg("out"));
   m.def("moe_w4_gemm", &moe_w4_gemm, pybind11::arg("x"), pybind11::arg("src_div"), pybind11::arg("codes"),
         pybind11::arg("zeros"), pybind11::arg("scales"), pybind11::arg("N"), pybind11::arg("K"), pybind11::arg("g"),
         pybind11::arg("counts"), pybind11::arg("lists"), pybind11::arg("part"));

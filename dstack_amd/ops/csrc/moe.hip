@@ -436,6 +436,7 @@ extern "C" hipError_t dsa_moe_route(const void* h, long ldh, const void* gate, c
 // ================================================================================================
 // Split-K reduces, fused with what follows the GEMM
 // ================================================================================================
+// (a block per pair or per row, so these two take the prefill GEMM's row counts too: moe_prefill.hip)
 // a[p][n] = bf16(silu(g) u), g = sum_s part[s][p][n], u = sum_s part[s][p][F + n] in the order s = 0, 1, ..
 // (fp32, one rounding), for the pairs of live rows; 4 columns per thread
 __global__ __launch_bounds__(256) void moe_swiglu_kernel(const float* __restrict__ part, const int* __restrict__ live,
@@ -450,13 +451,13 @@ __global__ __launch_bounds__(256) void moe_swiglu_kernel(const float* __restrict
   }
   f32x4 o;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) o[i] = g[i] / (1.f + expf(-g[i])) * u[i];
+  for (int i = 0; i < 4; ++i) o[i] = moe_silu_mul(g[i], u[i]);
   stream::store_bf16x4(A + (long)p * F + n, o);
 }
 
 extern "C" hipError_t dsa_moe_swiglu(const float* part, const int* live, void* A, int R, int k, int F, int S,
                                      hipStream_t st) {
-  if (R < 1 || R > MOE_MAXR || k < 1 || k > MOE_MAXK || F < 4 || F % 4 || S < 1) return hipErrorInvalidValue;
+  if (R < 1 || R > MOE_PREFILL_MAXR || k < 1 || k > MOE_MAXK || F < 4 || F % 4 || S < 1) return hipErrorInvalidValue;
   moe_swiglu_kernel<<<dim3((F / 4 + 255) / 256, R * k), 256, 0, st>>>(part, live, (bf16_t*)A, R * k, k, F, S);
   return hipGetLastError();
 }
@@ -486,7 +487,7 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(const float* __restric
 
 extern "C" hipError_t dsa_moe_combine(const float* part, const float* topk_w, const int* live, void* Y, long ldy, int R,
                                       int k, int N, int S, hipStream_t st) {
-  if (R < 1 || R > MOE_MAXR || k < 1 || k > MOE_MAXK || N < 4 || N % 4 || ldy % 4 || ldy < N || S < 1)
+  if (R < 1 || R > MOE_PREFILL_MAXR || k < 1 || k > MOE_MAXK || N < 4 || N % 4 || ldy % 4 || ldy < N || S < 1)
     return hipErrorInvalidValue;
   moe_combine_kernel<<<dim3((N / 4 + 255) / 256, R), 256, 0, st>>>(part, topk_w, live, (bf16_t*)Y, ldy, R * k, k, N, S);
   return hipGetLastError();

@@ -15,6 +15,7 @@ using stream::f32x4;
 using stream::i32x4;
 
 constexpr int MOE_MAXR = 256;  // token rows
+constexpr int MOE_PREFILL_MAXR = 2048;  // token rows of moe_prefill.hip, and of moe_swiglu / moe_combine after either
 constexpr int MOE_MAXK = 8;    // experts per token
 constexpr int MOE_BK = 128;    // K elements per step
 constexpr int MOE_NF = 2;      // 16-row weight fragments per wave
@@ -54,6 +55,10 @@ __device__ __forceinline__ void moe_read_x(const char* row, int r, int gq, bf16x
 __device__ __forceinline__ f32x4 moe_mfma(const i32x4& a, const bf16x8& b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), b, c, 0, 0, 0);
 }
+
+// silu(g) u in fp32: what moe_swiglu (moe.hip) and the gate/up epilogue of moe_prefill_gemm (moe_prefill.hip)
+// round to bf16
+__device__ __forceinline__ float moe_silu_mul(float g, float u) { return g / (1.f + expf(-g)) * u; }
 
 }  // namespace moe
 }  // namespace dsa

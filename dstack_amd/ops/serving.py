@@ -1147,8 +1147,145 @@ def moe_fine_mlp(h: torch.Tensor, router: torch.Tensor, wgu: torch.Tensor, wdown
 
 
 # ----------------------------------------------------------------------------------------------
-# The same MLP over W4 (AWQ) experts: csrc/moe_w4.hip
+# The same MLP for a prefill of more than 256 rows, on a tiled grouped GEMM: csrc/moe_prefill.hip
 # ----------------------------------------------------------------------------------------------
+MOE_PREFILL_MAX_ROWS = 2048  # token rows of one moe_prefill_mlp
+
+
+def moe_prefill_tile(R: int, k: int, E: int) -> int:
+    """Pairs per tile of the prefill expert GEMM, from the shape alone: 128 where an expert has 96 pairs or more
+    on average (``R k / E``), else 64."""
+    return 128 if R * k >= 96 * E else 64
+
+
+def moe_prefill_tiles(R: int, k: int, E: int, tile: int) -> int:
+    """Tiles that hold any routing: every expert's pairs padded to whole tiles take at most this many."""
+    return R * k // tile + min(E, R * k)
+
+
+def moe_prefill_gemm_supported(N: int, K: int) -> bool:
+    """``W`` [E, N, K] shapes the prefill expert GEMM runs: N % 128 == 0, K % 64 == 0, K >= 128."""
+    return N > 0 and N % 128 == 0 and K >= 128 and K % 64 == 0
+
+
+def moe_prefill_plan(topk_e: torch.Tensor, live: torch.Tensor, E: int, tile: int | None = None, out=None):
+    """The live pairs ``row * k + j`` of ``topk_e`` int32 [R, k] (R <= 2048, E <= 128) grouped by expert into
+    tiles of ``tile`` pairs (:func:`moe_prefill_tile` if None), with no host read: ``tile_e`` int32 [tiles], a
+    tile's expert or -1 past the last tile, and ``pairs`` int32 [tiles, tile], -1 where a tile is ragged or
+    unused (tiles = :func:`moe_prefill_tiles`).  The order of an expert's pairs is free.  ``out``: the two
+    tensors to write."""
+    R, k = topk_e.shape
+    tile = tile or moe_prefill_tile(R, k, E)
+    tiles = moe_prefill_tiles(R, k, E, tile)
+    if out is None:
+        out = (torch.empty(tiles, dtype=torch.int32, device=topk_e.device),
+               torch.empty(tiles, tile, dtype=torch.int32, device=topk_e.device))
+    tile_e, pairs = out
+    if _ext.use_hip(topk_e):
+        _ext.require().moe_prefill_plan(topk_e, live, E, tile_e, pairs)
+        return out
+    tile_e.fill_(-1)
+    pairs.fill_(-1)
+    flat = torch.where((live > 0)[:, None], topk_e, torch.full_like(topk_e, -1)).flatten()
+    t = 0
+    for e in range(E):
+        mine = torch.nonzero(flat == e).flatten().to(torch.int32)
+        n = -(-mine.numel() // tile)
+        tile_e[t : t + n] = e
+        pairs[t : t + n].view(-1)[: mine.numel()] = mine
+        t += n
+    return out
+
+
+def _moe_prefill_product(x, src_div, W, tile_e, pairs):
+    """fp32 [R k, N]: ``x[p // src_div] @ W[expert(p)]^T`` accumulated in fp64 for the plan's pairs, zeros elsewhere."""
+    prod = torch.zeros(x.shape[0] * src_div, W.shape[1], dtype=torch.float32, device=x.device)
+    for t, e in enumerate(tile_e.tolist()):
+        mine = pairs[t][pairs[t] >= 0].long()
+        if e >= 0 and mine.numel():
+            prod[mine] = (x[mine // src_div].double() @ W[e].double().t()).float()
+    return prod
+
+
+def moe_prefill_gemm(x: torch.Tensor, src_div: int, W: torch.Tensor, tile_e: torch.Tensor, pairs: torch.Tensor, k: int,
+                     part: torch.Tensor | None = None) -> torch.Tensor:
+    """Tiled grouped GEMM over a :func:`moe_prefill_plan` of ``k`` experts per token: ``part[0, p] = x[p // src_div]
+    @ W[expert(p)]^T`` in fp32 [1, R k, N] for the plan's pairs (other rows are not written) -- the tensor
+    :func:`moe_gemm` writes with one K slice, so :func:`moe_combine` reads it.  ``x`` bf16 [R, K] with ``src_div =
+    k`` or [R k, K] with ``src_div = 1``; ``W`` bf16 [E, N, K], N % 128 == 0, K % 64 == 0, K >= 128.  Without the
+    kernels: fp64 sums, zeros for the other rows."""
+    if not _ext.use_hip(x):
+        return _moe_prefill_product(x, src_div, W, tile_e, pairs)[None]
+    if part is None:
+        part = torch.empty(1, x.shape[0] * src_div, W.shape[1], dtype=torch.float32, device=x.device)
+    _ext.require().moe_prefill_gemm(x, src_div, W, tile_e, pairs, k, part)
+    return part
+
+
+def moe_prefill_gemm_swiglu(x: torch.Tensor, src_div: int, W: torch.Tensor, tile_e: torch.Tensor, pairs: torch.Tensor,
+                            k: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The gate/up form of :func:`moe_prefill_gemm`: ``W`` [E, 2F, K] holds gate rows, then up rows, and the
+    epilogue writes ``a[p] = dtype(silu(g) * u)`` bf16 [R k, F] for the plan's pairs straight from the fp32
+    accumulators -- the bits of :func:`moe_swiglu` over :func:`moe_prefill_gemm`'s ``part``, which is never
+    written.  Other rows of ``a`` are not written."""
+    if out is None:
+        out = torch.zeros(x.shape[0] * src_div, W.shape[1] // 2, dtype=torch.bfloat16, device=x.device)
+    if _ext.use_hip(x):
+        _ext.require().moe_prefill_gemm(x, src_div, W, tile_e, pairs, k, out)
+        return out
+    rows = pairs[pairs >= 0].long()
+    g, u = _moe_prefill_product(x, src_div, W, tile_e, pairs)[rows].chunk(2, dim=-1)
+    out[rows] = (torch.nn.functional.silu(g) * u).to(out.dtype)
+    return out
+
+
+class MoePrefillWorkspace:
+    """The buffers of :func:`moe_prefill_mlp` for up to ``rows`` (at most 2048) rows of one model shape, allocated
+    once: routing, the plan at its largest, the per-pair activations and the fp32 down products."""
+
+    def __init__(self, E: int, k: int, D: int, F: int, device, rows: int = MOE_PREFILL_MAX_ROWS):
+        moe_check(E, k, MOE_FINE_MAX_EXPERTS, "num_experts")
+        if not (moe_prefill_gemm_supported(2 * F, D) and moe_prefill_gemm_supported(D, F)) or not 1 <= rows <= MOE_PREFILL_MAX_ROWS:
+            raise ValueError(f"mixture of experts: the prefill expert GEMM takes up to {MOE_PREFILL_MAX_ROWS} rows, a hidden "
+                             f"size ({D}) and an FFN size ({F}) that are multiples of 64 and at least 128")
+        self.E, self.k, self.D, self.F, self.rows = E, k, D, F, rows
+        i32, P = dict(dtype=torch.int32, device=device), rows * k
+        self.topk_e, self.topk_w = torch.zeros(P, **i32), torch.zeros(P, dtype=torch.float32, device=device)
+        self.counts, self.lists = torch.zeros(E, **i32), torch.zeros(E * MOE_MAX_ROWS, **i32)  # (moe_route's, unused)
+        self.tile_e = torch.zeros(moe_prefill_tiles(rows, k, E, 64), **i32)
+        self.pairs = torch.zeros(moe_prefill_tiles(rows, k, E, 128) * 128, **i32)  # (128-pair tiles pad the most)
+        self.a = torch.zeros(P, F, dtype=torch.bfloat16, device=device)
+        self.part = torch.zeros(P * D, dtype=torch.float32, device=device)
+
+    def nbytes(self) -> int:
+        return self.part.numel() * 4 + self.a.numel() * 2
+
+
+def moe_prefill_mlp(h: torch.Tensor, router: torch.Tensor, wgu: torch.Tensor, wdown: torch.Tensor, k: int,
+                    live: torch.Tensor, ws: MoePrefillWorkspace) -> torch.Tensor:
+    """The MoE MLP of up to ``ws.rows`` rows (a prefill) on the tiled grouped GEMM: route (the decode router, 256
+    rows a call), plan, gate/up GEMM with the SwiGLU in its epilogue, down GEMM, weighted sum (:func:`moe_combine`).
+    Every expert's weights are read once per tile of its pairs, not once per 256 rows.  No host read.  ``wgu`` bf16
+    [E, 2F, D], ``wdown`` bf16 [E, D, F]; ``ws``: :class:`MoePrefillWorkspace`."""
+    R, E, D, F = h.shape[0], router.shape[0], ws.D, ws.F
+    assert R <= ws.rows and (E, k) == (ws.E, ws.k), (R, E, k)
+    if h.stride(-1) != 1 or h.stride(0) % 8 or h.data_ptr() % 16:
+        h = h.contiguous()
+    P, n = R * k, MOE_MAX_ROWS
+    topk_e, topk_w = ws.topk_e[:P].view(R, k), ws.topk_w[:P].view(R, k)
+    if not _ext.use_hip(h):
+        topk_e, topk_w = moe_route_ref(h, router, live, k)[:2]
+    for i in range(0, R if _ext.use_hip(h) else 0, n):  # (the router GEMM is tiny; its counts and lists are not used)
+        r = min(n, R - i)
+        moe_route(h[i : i + r], router, live[i : i + r], k,
+                  out=(topk_e[i : i + r], topk_w[i : i + r], ws.counts, ws.lists[: E * r].view(E, r)))
+    tile = moe_prefill_tile(R, k, E)
+    tiles = moe_prefill_tiles(R, k, E, tile)
+    plan = moe_prefill_plan(topk_e, live, E, tile, out=(ws.tile_e[:tiles], ws.pairs[: tiles * tile].view(tiles, tile)))
+    a = moe_prefill_gemm_swiglu(h, k, wgu, *plan, k, out=ws.a[:P])
+    part = moe_prefill_gemm(a, 1, wdown, *plan, k, part=ws.part[: P * D].view(1, P, D))
+    return moe_combine(part, topk_w, live)
+
 # A stacked W4 expert weight [E, N, K] is the triple ``(codes uint8 [E, N, K/2], zeros uint8 [E, N, K/g],
 # scales fp16 [E, N, K/g])``, every expert in :func:`w4_shuffle`'s stored form (K % 128 == 0 here).
 def moe_w4_gemm_split(R: int, k: int, E: int, N: int, K: int) -> int:

@@ -450,6 +450,11 @@ class ServingLlama:
         self.moe_fine = bool(self.E) and spec.family == "qwen3_moe"
         self.moe_ws = sops.MoeWorkspace(self.E, self.topk, cfg.dim, cfg.ffn_dim, self.device, w4_group=self.moe_w4_group,
                                         fine=self.moe_fine) if self.E and self.hip else None
+        # (qwen3_moe, more than 256 rows: the tiled grouped GEMM of csrc/moe_prefill.hip from a workspace of its own,
+        # where it covers the shapes; Mixtral and AWQ experts keep their eager prefill)
+        self.moe_prefill_ws = sops.MoePrefillWorkspace(self.E, self.topk, cfg.dim, cfg.ffn_dim, self.device) \
+            if self.moe_fine and self.hip and sops.moe_prefill_gemm_supported(2 * cfg.ffn_dim, cfg.dim) \
+            and sops.moe_prefill_gemm_supported(cfg.dim, cfg.ffn_dim) else None
         # how the GPU runs (h, router, wgu, wdown, live), by whether the layer's experts are ``Awq4Experts``: up to 256
         # rows on the kernels, more rows eagerly (with the W4 scratch).  The closures hold no reference to the model:
         # it is freed when its last user lets go of it, not at a later collection
@@ -1289,8 +1294,10 @@ class ServingLlama:
         others come out as zeros).  CPU: ``ref.moe_mlp``, AWQ experts dequantized to fp32 first.  GPU:
         up to 256 rows (a decode batch, a verify step, a short prefill) on the kernels of the experts'
         form (``sops.moe_mlp``, ``moe_w4_mlp`` or ``moe_fine_mlp``) -- no host read, so the step can be
-        captured.  More rows (prefill): qwen3_moe in chunks of 256 rows on the same kernels, ``live``
-        sliced alongside; the others on one library GEMM pair per non-empty expert
+        captured.  More rows (prefill): qwen3_moe on the tiled grouped GEMM (``sops.moe_prefill_mlp``)
+        in slices of ``sops.MOE_PREFILL_MAX_ROWS`` rows, ``live`` sliced alongside, which reads every
+        expert once per tile of its pairs -- or, at a shape that GEMM does not cover, in chunks of 256
+        rows on the decode kernels; the others on one library GEMM pair per non-empty expert
         (``sops.moe_mlp_eager``; ``moe_w4_mlp_eager`` dequantizes one expert at a time into the W4
         scratch), which reads the routing counts on the host once per layer."""
         router, wgu, wdown, live = L["router"], L["wgu"], L["wdown"], self._moe_live
@@ -1303,6 +1310,10 @@ class ServingLlama:
         n = sops.MOE_MAX_ROWS
         if h.shape[0] <= n:
             return kernels(h, router, wgu, wdown, live)
+        if self.moe_prefill_ws is not None:
+            n = sops.MOE_PREFILL_MAX_ROWS
+            return torch.cat([sops.moe_prefill_mlp(h[i : i + n], router, wgu, wdown, self.topk, live[i : i + n], self.moe_prefill_ws)
+                              for i in range(0, h.shape[0], n)])
         if self.moe_fine:  # through the one workspace
             return torch.cat([kernels(h[i : i + n], router, wgu, wdown, live[i : i + n]) for i in range(0, h.shape[0], n)])
         return eager(h, router, wgu, wdown, live, self._w4_scratch)

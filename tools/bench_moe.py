@@ -18,7 +18,10 @@ FFN 768, 128 experts, top-8) or at Qwen3-235B-A22B's (hidden 4096, FFN 1536) wit
 ``moe_gemm`` can run too: there it runs beside ``moe_fine_gemm`` on the same routing.  Gate/up and down GEMM,
 the weight GB/s of the chosen experts, the whole MLP on the kernels against ``moe_mlp_eager``.
 
-    python tools/bench_moe.py [--w4 | --fine 30b|235b] [--out FILE]  # ROWS=1,16,64,256 REPS=5 ITERS=20
+``--prefill``: the MLP of a prefill of 384 .. 4096 rows at Qwen3-30B-A3B's shapes on ``moe_prefill_mlp``
+(csrc/moe_prefill.hip, the tiled grouped GEMM) against ``moe_fine_mlp`` over 256-row slices, µs and TFLOP/s.
+
+    python tools/bench_moe.py [--w4 | --fine 30b|235b | --prefill] [--out FILE]  # ROWS=1,16,64,256 REPS=5 ITERS=20
 """
 import argparse
 import os
@@ -145,14 +148,47 @@ def fine_table(dev, draw, shape, rows, reps, iters):
     return text
 
 
+def prefill_table(dev, draw, rows, reps, iters):
+    """The whole MLP of a prefill of R rows on ``moe_prefill_mlp`` (slices of 2048 rows, as the engine runs it)
+    against ``moe_fine_mlp`` over 256-row slices, the path it replaces; TFLOP/s over the 6 R k D F flops of the
+    routed pairs."""
+    E, TOPK, D, F = FINE_SHAPES["30b"]
+    router, wgu, wdown = draw(E, D, sd=0.02), draw(E, 2 * F, D, sd=0.02), draw(E, D, F, sd=0.02)
+    ws, pws = sops.MoeWorkspace(E, TOPK, D, F, dev, fine=True), sops.MoePrefillWorkspace(E, TOPK, D, F, dev)
+    lines = [f"# {torch.cuda.get_device_name(0)}; Qwen3-MoE MLP of a prefill (hidden {D}, FFN {F}, {E} experts, top-{TOPK}); "
+             f"us per call, median of {reps} x {iters} calls (min..max)",
+             "# rows tile | moe_prefill_mlp us, TFLOP/s | moe_fine_mlp in 256-row slices us, TFLOP/s | slices/prefill"]
+
+    def run(mlp, w, n, h, live):
+        return torch.cat([mlp(h[i : i + n], router, wgu, wdown, TOPK, live[i : i + n], w) for i in range(0, h.shape[0], n)])
+
+    for R in rows:
+        hs = [draw(R, D, sd=1.0) for _ in range(4)]
+        live = torch.ones(R, dtype=torch.int32, device=dev)
+        paths = {"prefill": lambda i: run(sops.moe_prefill_mlp, pws, sops.MOE_PREFILL_MAX_ROWS, hs[i % 4], live),
+                 "slices": lambda i: run(sops.moe_fine_mlp, ws, sops.MOE_MAX_ROWS, hs[i % 4], live)}
+        t, med = measure(paths, reps, iters)
+        cell = {name: f"{med[name]:8.1f} ({min(v):.0f}..{max(v):.0f}) {6 * R * TOPK * D * F / med[name] / 1e6:6.1f}"
+                for name, v in t.items()}
+        lines.append(f"{R:6d} {sops.moe_prefill_tile(min(R, sops.MOE_PREFILL_MAX_ROWS), TOPK, E):4d} | {cell['prefill']} | "
+                     f"{cell['slices']} | {med['slices'] / med['prefill']:.2f}x")
+        print(lines[-1], flush=True)
+    text = "\n".join(lines) + "\n"
+    print(text)
+    return text
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="also write the table to this file")
     ap.add_argument("--fine", choices=sorted(FINE_SHAPES), default=None,
                     help="moe_fine_gemm at Qwen3-30B-A3B's shapes, or at Qwen3-235B's with 64 experts beside moe_gemm")
     ap.add_argument("--w4", action="store_true", help="W4 experts (moe_w4_gemm) beside the bf16 kernels")
+    ap.add_argument("--prefill", action="store_true",
+                    help="moe_prefill_mlp beside moe_fine_mlp in 256-row slices at Qwen3-30B-A3B's shapes (ROWS defaults to "
+                         "384,512,1024,2048,4096)")
     args = ap.parse_args()
-    rows = [int(r) for r in os.getenv("ROWS", "1,16,64,256").split(",")]
+    rows = [int(r) for r in os.getenv("ROWS", "384,512,1024,2048,4096" if args.prefill else "1,16,64,256").split(",")]
     reps, iters = int(os.getenv("REPS", "5")), int(os.getenv("ITERS", "20"))
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(0)
@@ -160,14 +196,16 @@ def main():
     def draw(*shape, sd):
         return torch.empty(*shape, dtype=torch.bfloat16, device=dev).normal_(0.0, sd, generator=g)
 
-    if args.fine:
+    if args.prefill:
+        text = prefill_table(dev, draw, rows, reps, iters)
+    elif args.fine:
         text = fine_table(dev, draw, args.fine, rows, reps, iters)
     else:
         router, wgu, wdown = draw(E, D, sd=0.02), draw(E, 2 * F, D, sd=0.02), draw(E, D, F, sd=0.02)
         ws = sops.MoeWorkspace(E, TOPK, D, F, dev)
-    if args.w4 and not args.fine:
+    if args.w4 and not args.fine and not args.prefill:
         text = w4_table(dev, draw, router, wgu, wdown, ws, rows, reps, iters)
-    if args.w4 or args.fine:
+    if args.w4 or args.fine or args.prefill:
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:
